@@ -36,12 +36,12 @@ timed region (init_s); a complete cold solve is reported as time_to_converge_s, 
 pays per call, src/interface_c/pogs_c.cpp:19-20) and reports every cycle and the slowest.
 
 value = N * K / T: iterations of one per-GPU shard per second, summed over ranks (at N = 1 the
-ADMM it/s of the configuration).  T is the max over ranks of the time of exactly K steps
-between barrier + synchronize on both sides; as many such windows are timed back to back as make
-the timed stretch a WHOLE NUMBER OF SOLVES (`windows`, `window_s`, `windows_cover`; pick_windows) and
-their mean is reported: the iterations of a solve do not all cost the same (a sparse solve's CGLS
-projections take 4 steps early, 1 in the middle, 2-3 at the end), and the metric is a solve's
-iterations over its loop time.
+ADMM it/s of the configuration); ms_per_step = T / K.  T is the max over ranks of the time of
+exactly K = --steps steps, after W = --warmup, between barrier + synchronize on both sides.  The
+iterations of a solve do not all cost the same (a sparse solve's CGLS projections take 4 steps early,
+1 in the middle, 2-3 at the end) and the metric is a solve's iterations over its loop time (SURVEY.md
+section 8(d)): a K that spans whole solves measures that, a shorter one the stretch it covers
+(`steps_cover`).
 
 Inputs are resident in HBM when the timed region starts.  The JSON line carries `roofline`
 (the dominant kernel, timed with HIP events on the solver's stream over the timed region;
@@ -64,6 +64,12 @@ OUTPUT: two lines on stdout.  First `BENCH_DETAIL {...}`: the long record, every
 {"metric", at most 6000 characters, with `roofline`, `cpu_baseline`, the wall-clock and parity scalars of the
 headline workload and a short block (value, roofline, parity, CPU figure) per secondary workload -- the driver
 parses the last line out of an 8 KB tail of stdout.
+
+--dump-outputs DIR: after the timed steps of each workload, what its last step computed -- x, y, l, mu, optval of
+the solve that step belongs to, stopped there (last_step_outputs) -- as DIR/<config>_<name>.npy, float32 or
+float64, a vector longer than 2^20 entries as a fixed seeded sample of them, 64 MB at most in all.  The inputs
+are the same in every run with the same arguments (seeded generators), so two builds can be compared output
+for output.
 
 CPU leg.  Dense: the compiled reference in
 both BLAS builds -- oracle/_ref/libpogs_cpu_openblas.so (scipy's OpenBLAS, which threads its
@@ -130,7 +136,15 @@ def parse():
                     help="time only the best BLAS build of the reference (what an N > 1 run does while the other ranks wait)")
     ap.add_argument("--cpu-full", action="store_true", help="run the reference to convergence instead (c2 on the GPU "
                                                             "box's host: max_iter, about twenty minutes)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed, per workload, as DIR/<config>_<name>.npy "
+                         "(last_step_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
+    return args
 
 
 def maybe_spawn(args):
@@ -394,28 +408,55 @@ def cpu_baseline(name, cfg, A_host, f, g, args, engine, world=1):
     return out, live
 
 
-def pick_windows(K, L, per_step_s, min_s=0.25, max_windows=40):
-    """Number of back-to-back windows of K steps for a workload whose solve takes L iterations: W K as close to a
-    whole number k of solves as W <= max_windows allows, the smallest k that makes the timed stretch at least `min_s`
-    seconds.  Returns (W, fraction of a solve by which W K misses k L)."""
-    if K >= 3 * L:
-        return 1, abs(K - round(K / L) * L) / float(K)
-    best = None
-    for k in range(1, 33):
-        w = max(1, int(round(k * L / float(K))))
-        if w > max_windows:
-            break
-        err = abs(w * K - k * L) / float(L)
-        long_enough = w * K * per_step_s >= min_s
-        # (a stretch that stays too short whatever k: the longest one that is still close to whole solves)
-        cand = (0, round(err, 3), w) if long_enough else (1, 0 if err <= 0.06 else 1, -w)
-        if best is None or cand < best[0]:
-            best = (cand, w, err)
-        if long_enough and err <= 0.06:
-            break
-    if best is None:
-        return max(1, min(max_windows, int(round(L / float(K))))), 1.0
-    return best[1], best[2]
+DUMP_MAX_BYTES = 64 << 20    # --dump-outputs: every array of one run together
+DUMP_MAX_ELEMS = 1 << 20     # a longer output is written as a fixed, seeded sample of this many entries (sample_output)
+
+
+def last_step_outputs(solver, f, g, res, steps_run, restarts):
+    """--dump-outputs: what a caller receives from the solve that the last timed step belongs to, stopped at that step.
+    The run's steps are iterations of back-to-back cold solves of L = res["iterations"] + 1 iterations each
+    (PogsAmdIterate), so after `steps_run` steps (warm-up and timed) with `restarts` cold starts the last step was
+    iteration p of its solve; the same handle solves (f, g) again with max_iter = p and its result -- x, y, l, mu
+    (y, l: this rank's rows) and optval -- is returned."""
+    import numpy as np
+
+    L = int(res["iterations"]) + 1
+    if restarts != (steps_run - 1) // L:
+        raise RuntimeError("the run restarted %d times in %d steps, not every %d steps: its last step is not iteration "
+                           "(steps - 1) %% L + 1 of a solve" % (restarts, steps_run, L))
+    p = (steps_run - 1) % L + 1
+    r = solver.solve(f, g, max_iter=p)
+    if r["iterations"] + 1 != p:
+        raise RuntimeError("the solve capped at %d iterations stopped after %d" % (p, r["iterations"] + 1))
+    return {"x": r["x"], "y": r["y"], "l": r["l"], "mu": r["mu"], "optval": np.array([r["optval"]], np.float64)}
+
+
+def sample_output(v):
+    """`v` whole if it has at most DUMP_MAX_ELEMS entries, else the same DUMP_MAX_ELEMS positions (a function of its
+    length alone) of it in ascending order."""
+    import numpy as np
+
+    v = np.ravel(v)
+    if v.size <= DUMP_MAX_ELEMS:
+        return v
+    return v[np.sort(np.random.default_rng(20240611).choice(v.size, DUMP_MAX_ELEMS, replace=False))]
+
+
+def write_outputs(out_dir, prefix, outputs, written=0):
+    """Writes each array of `outputs` as out_dir/<prefix>_<name>.npy (float32 / float64, sample_output applied);
+    `written`: the bytes earlier calls of this run wrote.  Returns the new total."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in outputs.items():
+        v = sample_output(v)
+        if v.dtype not in (np.float32, np.float64):
+            raise TypeError("%s_%s: %s output" % (prefix, k, v.dtype))
+        written += v.nbytes
+        if written > DUMP_MAX_BYTES:
+            raise RuntimeError("--dump-outputs: more than %d bytes" % DUMP_MAX_BYTES)
+        np.save(os.path.join(out_dir, "%s_%s.npy" % (prefix, k)), v)
+    return written
 
 
 def csrc_sha16():
@@ -631,6 +672,7 @@ class Env:
                 self.wait_group = None
 
     wait_group = None
+    dump_bytes = 0   # written by --dump-outputs so far (all workloads of the run)
 
     def barrier(self):
         import torch
@@ -653,7 +695,7 @@ class Env:
 
 
 def run_config(env, name, with_cpu):
-    """One configuration: build, one cold solve, the timed windows.  Returns the JSON dict on rank 0
+    """One configuration: build, one cold solve, the timed steps.  Returns the JSON dict on rank 0
     (None elsewhere)."""
     import numpy as np
     import torch
@@ -726,38 +768,29 @@ def run_config(env, name, with_cpu):
     st_solve = solver.stats()
 
     solver.begin_run(f, g)
-    solver.iterate(args.warmup)
-    # exactly K steps between barriers, in as many back-to-back windows as make the timed stretch a whole number of
-    # SOLVES (pick_windows): the iterations of a solve do not cost the same (a CGLS projection takes 4 steps early in
-    # a C4 solve, 1 in its middle, 2-3 plus the exact-residual products at its end: 1.5 / 0.53 / 1.06 ms per iteration),
-    # and the metric is a solve's iterations over its loop time -- a window that covers the cheap
-    # middle of a solve would flatter it.  The iterations run periodically (a converged solve restarts from the cold
-    # start), so any stretch of k whole periods is unbiased whatever its phase.
-    per_step_guess = max(st_solve["t_loop_s"] / max(st_solve["iterations"], 1), 1e-6)
-    windows, cover = pick_windows(args.steps, int(res["iterations"]) + 1, per_step_guess)
-    if dist is not None:   # every rank must run the same number of windows (barriers): rank 0's choice
-        wt = torch.tensor([windows], dtype=torch.int64, device=env.coll_dev)
-        dist.broadcast(wt, 0)
-        windows = int(wt.item())
-    times = []
+    _, restarts = solver.iterate(args.warmup)
+    # exactly K = --steps steps between barriers.  The iterations of a solve do not cost the same (a CGLS projection
+    # takes 4 steps early in a C4 solve, 1 in its middle, 2-3 plus the exact-residual products at its end: 1.5 / 0.53 /
+    # 1.06 ms per iteration), and the metric is a solve's iterations over its loop time: the
+    # iterations run periodically (a converged solve restarts from the cold start), so K steps that span whole solves
+    # give that rate whatever their phase, a K much shorter than a solve gives the rate of the stretch it covers.
     solver.reset_stats()
-    for _ in range(windows):
-        env.barrier()
-        t0 = time.time()
-        solver.iterate(args.steps)
-        env.barrier()
-        elapsed = time.time() - t0
-        if dist is not None:
-            tt = torch.tensor([elapsed], dtype=torch.float64, device=env.coll_dev)
-            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-            elapsed = float(tt.item())
-        times.append(elapsed)
-    # the windows are consecutive stretches of the same real solves: their MEAN is the iteration rate
-    # (the median would drop the windows that hold a solve's dearer iterations -- a missed rho
-    # prediction's extra pass, the two-step CG projections late in a sparse solve)
-    elapsed = sum(times) / len(times)
+    env.barrier()
+    t0 = time.time()
+    _, n_restarts = solver.iterate(args.steps)
+    env.barrier()
+    elapsed = time.time() - t0
+    restarts += n_restarts
+    if dist is not None:
+        tt = torch.tensor([elapsed], dtype=torch.float64, device=env.coll_dev)
+        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+        elapsed = float(tt.item())
     st = solver.stats()
     nranks_comm = st.get("comm_nranks", 0)   # as ncclCommCount reports it (0: no communicator)
+    if args.dump_outputs:
+        outputs = last_step_outputs(solver, f, g, res, args.warmup + args.steps, restarts)
+        if rank == 0:
+            env.dump_bytes = write_outputs(args.dump_outputs, name, outputs, env.dump_bytes)
     solver.close()
 
     # create / solve / destroy, HANDLE_CYCLES times: what a caller of the one-shot ABI pays per call
@@ -876,7 +909,7 @@ def run_config(env, name, with_cpu):
         avg_ms = st["stream_ms"] / launches
         bytes_per_launch = st["stream_bytes"] / launches  # algorithmic, see DESIGN.md section 6
         achieved = bytes_per_launch / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
-        steps_total = args.steps * windows
+        steps_total = args.steps
         if sparse:
             nnz = A.nnz
             kernel = "spmv_sell_fin_kernel / spmv_sell_kernel (every SpMV of the loop: A p, A^T r, A x)"
@@ -930,10 +963,9 @@ def run_config(env, name, with_cpu):
             "value": its, "unit": "it/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": cfg["dtype"], "data": "synthetic",
-            "windows": windows, "window_s": times,
-            "windows_cover": "%d x %d = %d iterations = %.2f solves of %d" % (windows, args.steps, windows * args.steps,
-                                                                              windows * args.steps / float(res["iterations"] + 1),
-                                                                              res["iterations"] + 1),
+            "steps_cover": "%d iterations = %.2f solves of %d" % (args.steps, args.steps / float(res["iterations"] + 1),
+                                                                  res["iterations"] + 1),
+            "timed_iterations": st["iterations"],   # what the library counted between the two barriers
             # (the scalars a reader of the driver's record needs sit in `config` and `roofline`, which it keeps whole:
             # wall-clock-to-converge is half of BASELINE.json's metric)
             "config": {"workload": workload, "name": name, "rows_per_gpu": m, "cols": n, "projector": projector,
@@ -1090,7 +1122,7 @@ def summary_line(line):
         out["cpu_baseline"] = _pick(cb, ("value", "unit", "cores", "kind", "sample", "time_to_converge_s", "init_s", "loop_s",
                                          "iterations", "converged", "extrapolated", "host_threads_visible"))
     out.update(_pick(line, ("time_to_converge_s", "init_s", "loop_s", "solve_iterations", "solve_status",
-                            "time_to_converge_exact_setup_s", "setup_ms", "gram_tflops", "windows", "windows_cover")))
+                            "time_to_converge_exact_setup_s", "setup_ms", "gram_tflops", "steps_cover")))
     if "handle_cycles" in line:
         out["handle_cycles_max_time_to_converge_s"] = line["handle_cycles"]["max_time_to_converge_s"]
         out["handle_cycles_max_init_s"] = line["handle_cycles"]["max_init_s"]
@@ -1106,7 +1138,7 @@ def summary_line(line):
     out["detail"] = "stdout line before this one (prefix %r) and gpurun_out/bench_detail.json" % DETAIL_PREFIX.strip()
     out = _short(out)
     # a hard stop, never reached by the shapes above (tests/test_gpu_bench.py holds the line under the limit)
-    for drop in ("detail", "setup_ms", "windows_cover", "handle_cycles_max_init_s", "h2d_s"):
+    for drop in ("detail", "setup_ms", "steps_cover", "handle_cycles_max_init_s", "h2d_s"):
         if len(json.dumps(out)) <= SUMMARY_MAX_CHARS:
             break
         out.pop(drop, None)
@@ -1145,8 +1177,8 @@ def main():
     # the driver's invocation (no --config, one GPU): c3, c4 (with their CPU legs) and c2 in fp64 under the same clock
     if args.config is None and env.world == 1 and not args.no_secondary and not (args.m or args.n) \
             and args.projector == "default":
-        keep = ("metric", "value", "unit", "dtype", "ms_per_step", "steps", "windows", "window_s", "windows_cover", "config", "roofline",
-                "time_to_converge_s", "init_s", "handle_cycles", "solve_iterations", "solve_status", "setup_ms", "gram_tflops",
+        keep = ("metric", "value", "unit", "dtype", "ms_per_step", "steps", "steps_cover", "timed_iterations", "config",
+                "roofline", "time_to_converge_s", "init_s", "handle_cycles", "solve_iterations", "solve_status", "setup_ms", "gram_tflops",
                 "parity_vs_reference", "cpu_baseline", "exact_setup", "time_to_converge_exact_setup_s", "one_shot_host_call")
         sec = {}
         for name in ("c3", "c4", "c2f64"):

@@ -48,6 +48,7 @@ def test_default_invocation_carries_the_contract_fields_and_the_secondary_worklo
                 "vs_baseline", "dtype", "data", "config", "roofline"):
         assert key in d, key
     assert d["n_gpus"] == 1 and d["steps"] == 20 and d["warmup"] == 5 and d["unit"] == "it/s"
+    assert d["timed_iterations"] == 20 and all(s["timed_iterations"] == 20 for s in d["secondary"].values())
     assert d["config"]["name"] == "c2" and "configs[1]" in d["config"]["workload"] and "model" not in d["config"]
     assert d["config"]["rccl_nranks"] == 0
     assert d["vs_baseline"] is None and d["dtype"] == "f32" and d["scaling"] == "weak"

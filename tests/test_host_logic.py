@@ -243,24 +243,50 @@ def test_bench_extrapolates_the_cpu_leg_of_a_multi_gpu_line():
     assert bench.extrapolate_cpu({"value": None}, 8, 1, 1) == {"value": None}
 
 
-def test_bench_windows_cover_whole_solves():
-    """bench.py times exactly K steps per window; the windows together cover a whole number of solves, because the
-    iterations of a solve do not cost the same (C4: 1.5 ms early, 0.53 ms in the middle, 1.06 ms at the end) and the
-    metric is a solve's iterations over its loop time."""
+def test_bench_dump_outputs_are_the_last_timed_step(tmp_path):
+    """bench.py --dump-outputs: the run's steps are iterations of back-to-back cold solves of L iterations, so the last
+    of its W + K steps is iteration (W + K - 1) % L + 1 of a solve, and that solve is re-run capped there; a restart count
+    that does not fit is an error.  A vector longer than DUMP_MAX_ELEMS is written as the same seeded sample every time,
+    everything as float32 / float64, and a run never writes more than DUMP_MAX_BYTES."""
     import sys
 
     sys.path.insert(0, ROOT)
     import bench
 
-    for K, L, per_step in ((20, 359, 0.87e-3), (20, 106, 0.68e-3), (20, 189, 0.72e-3), (200, 359, 0.87e-3), (200, 106, 0.68e-3)):
-        w, err = bench.pick_windows(K, L, per_step)
-        solves = w * K / float(L)
-        assert 1 <= w <= 40 and abs(solves - round(solves)) <= 0.06 and err <= 0.06, (K, L, w, solves)
-        assert w * K * per_step >= 0.25
-    assert bench.pick_windows(20, 359, 0.87e-3)[0] == 18                 # one C4 solve
-    assert bench.pick_windows(1000, 106, 0.68e-3)[0] == 1               # K spans many solves already
-    w, _ = bench.pick_windows(20, 2500, 1e-3)                          # a solve longer than 40 windows: as many as allowed
-    assert w == 40
+    big = 2 * bench.DUMP_MAX_ELEMS + 5
+
+    class Solver:
+        def __init__(self):
+            self.max_iter = []
+
+        def solve(self, f, g, max_iter=2500):
+            self.max_iter.append(max_iter)
+            return {"x": np.arange(7, dtype=np.float32), "y": np.arange(big, dtype=np.float32),
+                    "l": -np.arange(big, dtype=np.float32), "mu": np.zeros(7, np.float32), "optval": 1.5,
+                    "iterations": min(max_iter, 106) - 1, "status": 0}
+
+    res = {"iterations": 105}      # a solve of 106 iterations (the C2 fixture's)
+    for steps, restarts, p in ((25, 0, 25), (106, 0, 106), (107, 1, 1), (220, 2, 8)):
+        s = Solver()
+        out = bench.last_step_outputs(s, None, None, res, steps, restarts)
+        assert s.max_iter == [p], (steps, s.max_iter)
+    with pytest.raises(RuntimeError):
+        bench.last_step_outputs(Solver(), None, None, res, 220, 1)
+    written = bench.write_outputs(str(tmp_path / "a"), "c2", out)
+    assert written == bench.write_outputs(str(tmp_path / "b"), "c2", out) <= bench.DUMP_MAX_BYTES
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["c2_l.npy", "c2_mu.npy", "c2_optval.npy", "c2_x.npy", "c2_y.npy"]
+    for nm in names:
+        v = np.load(tmp_path / "a" / nm)
+        assert v.dtype in (np.float32, np.float64) and np.array_equal(v, np.load(tmp_path / "b" / nm)), nm
+    assert np.array_equal(np.load(tmp_path / "a" / "c2_x.npy"), np.arange(7))
+    y = np.load(tmp_path / "a" / "c2_y.npy")
+    assert y.size == bench.DUMP_MAX_ELEMS and np.all(np.diff(y) > 0) and np.array_equal(np.load(tmp_path / "a" / "c2_l.npy"), -y)
+    assert np.load(tmp_path / "a" / "c2_optval.npy").tolist() == [1.5]
+    with pytest.raises(RuntimeError):
+        bench.write_outputs(str(tmp_path / "c"), "c2", out, written=bench.DUMP_MAX_BYTES - 8)
+    with pytest.raises(TypeError):
+        bench.write_outputs(str(tmp_path / "c"), "c2", {"i": np.arange(3)})
 
 
 def test_bench_contract_line_is_short_and_starts_with_metric(capsys, tmp_path, monkeypatch):
