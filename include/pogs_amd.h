@@ -148,7 +148,14 @@ typedef struct PogsAmdStats {
   double reserved[8];             /* [0] / [1]: one-pass iteration, rho predictions hit / missed;
                                      [2]: all-reduce calls issued by the handle so far;
                                      [3]: ranks of the handle's communicator as RCCL reports
-                                          them (ncclCommCount; 0 without row shards)             */
+                                          them (ncclCommCount; 0 without row shards);
+                                     [4]: after PogsAmdSolveBatchFn, the sum over its problems
+                                          of the iterations each one executed (`iterations` then
+                                          counts batch iterations, `matvecs` multi-vector passes
+                                          over A);
+                                     [5] / [6] / [7]: with options.profile, the same batch's
+                                          HIP-event time (ms), launch count and algorithmic bytes
+                                          of its multi-vector passes over A                       */
 } PogsAmdStats;
 
 /* Fill `out` (POGS_AMD_UNIQUE_ID_BYTES) with a fresh RCCL unique id (rank 0
@@ -206,6 +213,19 @@ int PogsAmdSolveFn(PogsAmdSolver *s, const PogsAmdFn *f, const PogsAmdFn *g,
 int PogsAmdBeginRunFn(PogsAmdSolver *s, const PogsAmdFn *f, const PogsAmdFn *g,
                       double rho, double abs_tol, double rel_tol, unsigned int max_iter,
                       int adaptive_rho, int gap_stop);
+
+/* Batched solves: k problems (1 <= k <= POGS_AMD_BATCH_MAX) on the handle's matrix, every pass over A shared by all
+ * of them.  f[j], g[j] as in PogsAmdSolveFn; rho: k values or NULL (1.0 each); tolerances, max_iter, adaptive_rho and
+ * gap_stop are shared, every problem starts cold, and a problem that stops is frozen while the others go on.
+ * Outputs are HOST arrays, problem j at offset j*n (x, mu) / j*m (y, l) / j (optval, final_iter, status);
+ * y, l, mu, optval may be NULL.  Returns 0 when the batch ran (status[j] holds each PogsStatus),
+ * POGS_ERROR when refused (PogsAmdLastError says why): k out of range, a sparse handle, m <= n, the CGLS projector,
+ * row shards, or a NULL x, final_iter or status.  The handle's solo state (a pending warm start included) is kept. */
+#define POGS_AMD_BATCH_MAX 16
+int PogsAmdSolveBatchFn(PogsAmdSolver *s, int k, const PogsAmdFn *f, const PogsAmdFn *g, const double *rho,
+                        double abs_tol, double rel_tol, unsigned int max_iter, unsigned int verbose,
+                        int adaptive_rho, int gap_stop, void *x, void *y, void *l, void *mu,
+                        double *optval, unsigned int *final_iter, int *status);
 
 /* Benchmark stepping.  PogsAmdBeginRun loads f/g and the solve parameters and
  * resets the ADMM state to the cold start; PogsAmdIterate then advances exactly

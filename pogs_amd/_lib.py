@@ -79,6 +79,10 @@ class PogsAmdStats(ctypes.Structure):
         d["spec_hits"], d["spec_misses"] = self.reserved[0], self.reserved[1]
         d["collectives"] = int(self.reserved[2])   # all-reduce calls issued by the handle so far
         d["comm_nranks"] = int(self.reserved[3])   # ranks of the communicator as RCCL reports them (0: no row shards)
+        # after a batched solve: problem-iterations summed over its problems; with profile, its passes over A
+        d["batch_problem_iters"] = int(self.reserved[4])
+        d["batch_pass_ms"], d["batch_pass_launches"] = self.reserved[5], int(self.reserved[6])
+        d["batch_pass_bytes"] = self.reserved[7]
         return d
 
 
@@ -118,6 +122,10 @@ class PogsAmdFn(ctypes.Structure):
 lib.PogsAmdSolveFn.argtypes = [c_void_p, ctypes.POINTER(PogsAmdFn), ctypes.POINTER(PogsAmdFn), c_double, c_double, c_double,
                                c_uint, c_uint, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                ctypes.POINTER(c_double), ctypes.POINTER(c_uint)]
+lib.PogsAmdSolveBatchFn.argtypes = [c_void_p, c_int, ctypes.POINTER(PogsAmdFn), ctypes.POINTER(PogsAmdFn), c_void_p,
+                                    c_double, c_double, c_uint, c_uint, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_void_p, c_void_p, c_void_p]
+BATCH_MAX = 16   # include/pogs_amd.h: POGS_AMD_BATCH_MAX
 lib.PogsAmdBeginRunFn.argtypes = [c_void_p, ctypes.POINTER(PogsAmdFn), ctypes.POINTER(PogsAmdFn), c_double, c_double, c_double,
                                   c_uint, c_int, c_int]
 lib.PogsAmdBeginRun.argtypes = [c_void_p] + [c_void_p] * 12 + [c_double, c_double, c_double, c_uint, c_int, c_int]
@@ -167,7 +175,7 @@ def pool_trim(device=-1):
 # Every symbol include/pogs_amd.h declares (checked by tests/test_abi.py).
 ABI_SYMBOLS = [
     "PogsD", "PogsS", "PogsSparseD", "PogsSparseS",
-    "PogsAmdDistUniqueId", "PogsAmdCreateDense", "PogsAmdCreateSparse", "PogsAmdSolve", "PogsAmdSolveFn", "PogsAmdBeginRun", "PogsAmdBeginRunFn",
+    "PogsAmdDistUniqueId", "PogsAmdCreateDense", "PogsAmdCreateSparse", "PogsAmdSolve", "PogsAmdSolveFn", "PogsAmdSolveBatchFn", "PogsAmdBeginRun", "PogsAmdBeginRunFn",
     "PogsAmdIterate", "PogsAmdSetWarmStart", "PogsAmdGetStats", "PogsAmdResetStats", "PogsAmdDestroy", "PogsAmdLastError",
     "PogsAmdPoolStats", "PogsAmdPoolTrim",
     "PogsAmdProxEval", "PogsAmdFuncEval", "PogsAmdProjSubgradEval", "PogsAmdGetEquil", "PogsAmdProject", "PogsAmdMul", "PogsAmdRandUniform",

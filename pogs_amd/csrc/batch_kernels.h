@@ -1,0 +1,75 @@
+// Kernels of the batched dense solves (dense_batch.h): multi-vector passes over a stored row-major matrix on the
+// matrix cores, and the per-problem element-wise stages.  Their own translation unit (batch_kernels.hip), so that the
+// per-shape code objects of the solo solver stay as small as they are.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "../../include/pogs_amd.h"
+#include "common.h"
+#include "prox.h"
+
+namespace pogs_amd {
+
+constexpr int kBatchMax = POGS_AMD_BATCH_MAX;
+
+// slot -> problem index of the problems a launch works on (slots >= nact are zero columns)
+struct BatchSlots {
+  int nact = 0;
+  int act[kBatchMax] = {};
+};
+
+constexpr int kBRowGroups = 4;
+constexpr int kBRowsPerWg = 16 * kBRowGroups;
+
+template <typename T>
+struct BatchVecArgs {
+  int n, m, bx, by;            // bx, by: vec_blocks(n), vec_blocks(m)
+  size_t ldx, ldy;
+  const FnView<T> *fg;         // [2 kb]: f of problem p at 2p, g at 2p + 1 (scaled)
+  BatchSlots sl;
+  T rho[kBatchMax], zs[kBatchMax];   // by problem index
+  T alpha;
+  const T *x_cur, *y_cur, *xt, *yt;
+  T *x12, *y12, *xtemp, *ytemp;
+  const T *x_new, *y_new;      // tail / exact stages
+  const T *zx, *zy;            // exact stage: A^T u (n), A x12 (m)
+  T *u;                        // exact prep: y12 + zs yt - yprev
+  double *part;                // [kb][bx + by][ns]
+};
+
+// Scalar sums of the problems of the slots: job q (blockIdx.x) adds records [b0, b1) of ns values from
+// part[p][nblk][ns] into out[p * kBatchRec + slot .. + ns).  Fixed order: thread stride, then dev::block_sum.
+constexpr int kBatchRec = 16;   // doubles per problem in the batch scalar block
+struct BatchSumJob {
+  const double *part;
+  int nblk, ns, b0, b1, slot;
+};
+struct BatchSumJobs {
+  BatchSumJob j[4];
+};
+// record layout of the batch scalar block (per problem)
+enum BatchRec : int { kBrPreX = 0, kBrPreY = 3, kBrTailX = 6, kBrTailY = 8, kBrExS = 10, kBrExR = 11, kBrFval = 12 };
+
+// Y[p][row] = sum_c M[row][c] X[p][c] for the problems p of sl (tri: kFull / kLower / kUpper of stream.h's Tri)
+template <typename T>
+void launch_batch_rows(int tri, const T *M, size_t ldm, int rows, int cols, int cols_pad, const T *X, size_t ldx, T *Y,
+                       size_t ldy, const BatchSlots &sl, hipStream_t s);
+// part[rb][p][c] = sum over the rows of row block rb of M[row][c] U[p][row]  (grid: column slabs x nrb row blocks)
+template <typename T>
+void launch_batch_cols(const T *M, size_t ldm, int rows, int cols_pad, int rows_per_block, int nrb, const T *U,
+                       size_t ldu, T *part, int kb, const BatchSlots &sl, hipStream_t s);
+// columns per slab of launch_batch_cols
+template <typename T>
+constexpr int batch_cols_slab() { return 64 / static_cast<int>(sizeof(T)) * 4; }
+// Z[p][c] = sum_rb part[rb][p][c] in row-block order (+ add[p][c]); columns >= cols are zero
+template <typename T>
+void launch_batch_cols_reduce(const T *part, int nrb, int kb, int cols, int cols_pad, const T *add, T *Z, size_t ldz,
+                              const BatchSlots &sl, hipStream_t s);
+// element-wise stages over x blocks (vec_blocks(n)) and y blocks (vec_blocks(m)), one grid row per slot
+template <typename T> void launch_batch_pre(const BatchVecArgs<T> &a, hipStream_t s);
+template <typename T> void launch_batch_tail(const BatchVecArgs<T> &a, hipStream_t s);
+template <typename T> void launch_batch_exact_u(const BatchVecArgs<T> &a, hipStream_t s);
+template <typename T> void launch_batch_exact(const BatchVecArgs<T> &a, hipStream_t s);
+void launch_batch_sums(const BatchSumJobs &jobs, int njobs, const BatchSlots &sl, double *out, hipStream_t s);
+
+}  // namespace pogs_amd

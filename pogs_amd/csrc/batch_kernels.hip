@@ -1,0 +1,362 @@
+// Kernels of the batched dense solves: see batch_kernels.h and dense_batch.h.
+//
+// Determinism: every multi-vector product is a v_mfma_*_16x16x4 chain, which is a k-ordered FMA chain per output
+// element, so the arithmetic of problem j depends neither on the other vectors nor on j's slot; the partials of
+// row blocks / waves are summed in a fixed order, and the row-block partition depends on the matrix shape only.
+#include "batch_kernels.h"
+#include "reduce.h"
+#include "stream.h"
+#include "vec_kernels.h"
+
+namespace pogs_amd {
+namespace {
+
+template <typename T>
+struct BatchMfma;
+template <>
+struct BatchMfma<float> {
+  typedef float acc __attribute__((ext_vector_type(4)));
+  static __device__ __forceinline__ acc mfma(float a, float b, acc c) {
+    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
+  }
+  // row of the 16 x 16 result held in register r of lane l (column l & 15)
+  static __device__ __forceinline__ int row(int lane, int r) { return 4 * (lane >> 4) + r; }
+};
+template <>
+struct BatchMfma<double> {
+  typedef double acc __attribute__((ext_vector_type(4)));
+  static __device__ __forceinline__ acc mfma(double a, double b, acc c) {
+    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
+  }
+  static __device__ __forceinline__ int row(int lane, int r) { return (lane >> 4) + 4 * r; }
+};
+
+// ---- K row dots: Y[p][row] = sum_c M[row][c] X[p][c] over the problems p of the slots -------------------------
+// A workgroup (4 waves) takes 64 rows (four 16-row groups); the waves walk the columns in interleaved steps of
+// 4 * VEC columns: lane l loads 16 bytes of row (l & 15) at column c0 + VEC (l >> 4) for each row group, and the
+// same 16 bytes of vector (l & 15), so element t of the load is MFMA t's k-slice (A[i][k] = M[r0 + i][c0 + VEC k + t],
+// B[k][j] = X_j[c0 + VEC k + t]).  One vector load serves four row groups.  The four waves' partial dots are added
+// in wave order through LDS.  TRI: the lower (c <= row) or upper (c >= row) triangle of a square factor only --
+// entries outside it are not read (and whatever the storage holds there does not matter); columns >= cols are zero.
+
+template <typename T, int TRI>
+__global__ void __launch_bounds__(256) batch_rows_kernel(const T *__restrict__ M, size_t ldm, int rows, int cols,
+                                                         int cols_pad, const T *__restrict__ X, size_t ldx,
+                                                         T *__restrict__ Y, size_t ldy, BatchSlots sl) {
+  using V = typename Vec16<T>::type;
+  using MF = BatchMfma<T>;
+  constexpr int VEC = Vec16<T>::N;
+  constexpr int STEP = 4 * VEC;   // columns per wave step
+  __shared__ T red[4][kBRowsPerWg][17];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int i = lane & 15, q = lane >> 4;
+  const int r0 = blockIdx.x * kBRowsPerWg;
+  int cbeg = 0, cend = cols;
+  if (TRI == kLower) cend = min(cols, r0 + kBRowsPerWg);
+  if (TRI == kUpper) cbeg = (r0 / (4 * STEP)) * (4 * STEP);
+  const bool vec_on = i < sl.nact;
+  const T *xp = X + (vec_on ? static_cast<size_t>(sl.act[i]) * ldx : 0);
+  typename MF::acc acc[kBRowGroups];
+#pragma unroll
+  for (int g = 0; g < kBRowGroups; ++g) acc[g] = typename MF::acc{0, 0, 0, 0};
+  for (int c0 = cbeg + w * STEP; c0 < cend; c0 += 4 * STEP) {
+    const int c = c0 + VEC * q;
+    V xv, av[kBRowGroups];
+    T *xe = reinterpret_cast<T *>(&xv);
+#pragma unroll
+    for (int t = 0; t < VEC; ++t) xe[t] = 0;
+    if (vec_on && c < cols_pad) xv = *reinterpret_cast<const V *>(xp + c);
+#pragma unroll
+    for (int g = 0; g < kBRowGroups; ++g) {
+      const int row = r0 + 16 * g + i;
+      T *ae = reinterpret_cast<T *>(&av[g]);
+#pragma unroll
+      for (int t = 0; t < VEC; ++t) ae[t] = 0;
+      bool ok = row < rows && c < cols_pad;
+      if (TRI == kLower) ok = ok && c <= row;
+      if (TRI == kUpper) ok = ok && c + VEC - 1 >= row;
+      if (ok) {
+        const T *rp = M + static_cast<size_t>(row) * ldm + c;
+        av[g] = (TRI == kFull) ? stream_load<V>(rp) : *reinterpret_cast<const V *>(rp);
+      }
+    }
+#pragma unroll
+    for (int g = 0; g < kBRowGroups; ++g) {
+      const int row = r0 + 16 * g + i;
+      T *ae = reinterpret_cast<T *>(&av[g]);
+#pragma unroll
+      for (int t = 0; t < VEC; ++t) {
+        bool keep = c + t < cols;
+        if (TRI == kLower) keep = keep && c + t <= row;
+        if (TRI == kUpper) keep = keep && c + t >= row;
+        acc[g] = MF::mfma(keep ? ae[t] : static_cast<T>(0), xe[t], acc[g]);
+      }
+    }
+  }
+#pragma unroll
+  for (int g = 0; g < kBRowGroups; ++g)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) red[w][16 * g + MF::row(lane, r)][i] = acc[g][r];
+  __syncthreads();
+  for (int o = threadIdx.x; o < kBRowsPerWg * 16; o += 256) {
+    const int rr = o >> 4, j = o & 15;
+    const int row = r0 + rr;
+    if (j < sl.nact && row < rows) {
+      const T v = ((red[0][rr][j] + red[1][rr][j]) + red[2][rr][j]) + red[3][rr][j];
+      Y[static_cast<size_t>(sl.act[j]) * ldy + row] = v;
+    }
+  }
+}
+
+// ---- K column sums, first stage: part[rb][p][c] = sum over the rows of row block rb of M[row][c] U[p][row] ------
+// A workgroup (4 waves) takes a slab of 16 VEC columns and one row block; the waves take interleaved quads of rows.
+// Lane l loads 16 bytes of row (4 quad + (l >> 4)) at column cs + VEC (l & 15) and the vector value U_(l & 15) of
+// that row, so element t of the load is MFMA t's A (rows of the 16 x 16 result = columns cs + VEC i + t) and the
+// vector value its B (k = the row within the quad).  Four quads are loaded per step.
+template <typename T>
+__global__ void __launch_bounds__(256) batch_cols_kernel(const T *__restrict__ M, size_t ldm, int rows, int cols_pad,
+                                                         int rows_per_block, const T *__restrict__ U, size_t ldu,
+                                                         T *__restrict__ part, int kb, BatchSlots sl) {
+  using V = typename Vec16<T>::type;
+  using MF = BatchMfma<T>;
+  constexpr int VEC = Vec16<T>::N;
+  constexpr int SLAB = 16 * VEC;
+  constexpr int QU = 4;   // quads per wave step
+  __shared__ T red[4][SLAB][17];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int i = lane & 15, k = lane >> 4;
+  const int cs = blockIdx.x * SLAB;
+  const int rb = blockIdx.y;
+  const int rlo = rb * rows_per_block, rhi = min(rows, rlo + rows_per_block);
+  const bool vec_on = i < sl.nact;
+  const T *up = U + (vec_on ? static_cast<size_t>(sl.act[i]) * ldu : 0);
+  const int c = cs + VEC * i;
+  typename MF::acc acc[VEC];
+#pragma unroll
+  for (int t = 0; t < VEC; ++t) acc[t] = typename MF::acc{0, 0, 0, 0};
+  for (int rq = rlo + 4 * w; rq < rhi; rq += 16 * QU) {
+    V av[QU];
+    T uv[QU];
+#pragma unroll
+    for (int u = 0; u < QU; ++u) {
+      const int row = rq + 16 * u + k;
+      T *ae = reinterpret_cast<T *>(&av[u]);
+#pragma unroll
+      for (int t = 0; t < VEC; ++t) ae[t] = 0;
+      uv[u] = 0;
+      if (row < rhi) {
+        if (c < cols_pad) av[u] = stream_load<V>(M + static_cast<size_t>(row) * ldm + c);
+        if (vec_on) uv[u] = up[row];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < QU; ++u) {
+      const T *ae = reinterpret_cast<const T *>(&av[u]);
+#pragma unroll
+      for (int t = 0; t < VEC; ++t) acc[t] = MF::mfma(ae[t], uv[u], acc[t]);
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < VEC; ++t)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) red[w][VEC * MF::row(lane, r) + t][i] = acc[t][r];
+  __syncthreads();
+  for (int o = threadIdx.x; o < SLAB * 16; o += 256) {
+    const int cc = o >> 4, j = o & 15;
+    const int col = cs + cc;
+    if (j < sl.nact && col < cols_pad) {
+      const T v = ((red[0][cc][j] + red[1][cc][j]) + red[2][cc][j]) + red[3][cc][j];
+      part[(static_cast<size_t>(rb) * kb + sl.act[j]) * cols_pad + col] = v;
+    }
+  }
+}
+
+// second stage: Z[p][c] = (sum_rb part[rb][p][c], in row-block order) (+ add[p][c]); columns >= cols are zero
+template <typename T>
+__global__ void __launch_bounds__(256) batch_cols_reduce_kernel(const T *__restrict__ part, int nrb, int kb, int cols,
+                                                                int cols_pad, const T *__restrict__ add, T *__restrict__ Z,
+                                                                size_t ldz, BatchSlots sl) {
+  const int col = blockIdx.x * 256 + threadIdx.x;
+  if (col >= cols_pad) return;
+  const int p = sl.act[blockIdx.y];
+  T v = 0;
+  for (int rb = 0; rb < nrb; ++rb) v += part[(static_cast<size_t>(rb) * kb + p) * cols_pad + col];
+  if (add) v = v + add[static_cast<size_t>(p) * ldz + col];
+  Z[static_cast<size_t>(p) * ldz + col] = col < cols ? v : static_cast<T>(0);
+}
+
+// ---- element-wise stages, blockIdx.y = slot; x blocks first, then y blocks ---------------------------------------
+// prox + over-relaxation (pogs.cpp:257-278; admm_pre_kernel), sums {w h, w^2, h^2}
+template <typename T>
+__global__ void __launch_bounds__(kVecTpb) batch_pre_kernel(BatchVecArgs<T> a) {
+  __shared__ double s_red[3 * (kVecTpb / 64)];
+  const int p = a.sl.act[blockIdx.y];
+  const bool is_x = static_cast<int>(blockIdx.x) < a.bx;
+  const int blk = is_x ? blockIdx.x : blockIdx.x - a.bx;
+  const int n = is_x ? a.n : a.m;
+  const size_t off = static_cast<size_t>(p) * (is_x ? a.ldx : a.ldy);
+  const FnView<T> fn = a.fg[2 * p + (is_x ? 1 : 0)];
+  const T *cur = (is_x ? a.x_cur : a.y_cur) + off;
+  const T *zt = (is_x ? a.xt : a.yt) + off;
+  T *z12 = (is_x ? a.x12 : a.y12) + off;
+  T *ztemp = (is_x ? a.xtemp : a.ytemp) + off;
+  const T rho = a.rho[p], zsc = a.zs[p];
+  double acc[3] = {0.0, 0.0, 0.0};
+  const int e = blk * kVecTpb + threadIdx.x;
+  if (e < n) {
+    const T prev = cur[e];
+    const T zs = zsc * zt[e];
+    const T v = prev - zs;
+    const T h = dev::ProxEval(fn.h[e], fn.a[e], fn.b[e], fn.c[e], fn.d[e], fn.e[e], v, rho);
+    const T wv = v - h;
+    z12[e] = h;
+    ztemp[e] = zs + a.alpha * h + (static_cast<T>(1) - a.alpha) * prev;
+    dev::prod_acc(acc[0], wv, h);
+    dev::prod_acc(acc[1], wv, wv);
+    dev::prod_acc(acc[2], h, h);
+  }
+  dev::block_sum<3, kVecTpb>(acc, s_red);
+  if (threadIdx.x == 0) {
+    double *out = a.part + (static_cast<size_t>(p) * (a.bx + a.by) + blockIdx.x) * 3;
+    out[0] = acc[0]; out[1] = acc[1]; out[2] = acc[2];
+  }
+}
+
+// projection tail (ProjTailOp): sums {(zprev - znew)^2, (z12 - znew)^2}, ztemp -= znew
+template <typename T>
+__global__ void __launch_bounds__(kVecTpb) batch_tail_kernel(BatchVecArgs<T> a) {
+  __shared__ double s_red[2 * (kVecTpb / 64)];
+  const int p = a.sl.act[blockIdx.y];
+  const bool is_x = static_cast<int>(blockIdx.x) < a.bx;
+  const int blk = is_x ? blockIdx.x : blockIdx.x - a.bx;
+  const int n = is_x ? a.n : a.m;
+  const size_t off = static_cast<size_t>(p) * (is_x ? a.ldx : a.ldy);
+  double acc[2] = {0.0, 0.0};
+  const int e = blk * kVecTpb + threadIdx.x;
+  if (e < n) {
+    const T zn = (is_x ? a.x_new : a.y_new)[off + e];
+    const T pv = (is_x ? a.x_cur : a.y_cur)[off + e] - zn;
+    const T qv = (is_x ? a.x12 : a.y12)[off + e] - zn;
+    dev::prod_acc(acc[0], pv, pv);
+    dev::prod_acc(acc[1], qv, qv);
+    (is_x ? a.xtemp : a.ytemp)[off + e] -= zn;
+  }
+  dev::block_sum<2, kVecTpb>(acc, s_red);
+  if (threadIdx.x == 0) {
+    double *out = a.part + (static_cast<size_t>(p) * (a.bx + a.by) + blockIdx.x) * 2;
+    out[0] = acc[0]; out[1] = acc[1];
+  }
+}
+
+// u = y12 + zs yt - yprev  (the y half of the exact dual residual, pogs.cpp:366-368)
+template <typename T>
+__global__ void __launch_bounds__(kVecTpb) batch_exact_u_kernel(BatchVecArgs<T> a) {
+  const int p = a.sl.act[blockIdx.y];
+  const int e = blockIdx.x * kVecTpb + threadIdx.x;
+  if (e >= a.m) return;
+  const size_t o = static_cast<size_t>(p) * a.ldy + e;
+  a.u[o] = a.y12[o] + a.zs[p] * a.yt[o] - a.y_cur[o];
+}
+
+// exact residuals (ExactRowOp / ExactColOp): y blocks sum (A x12 - y12)^2, x blocks (A^T u + x12 + zs xt - xprev)^2
+template <typename T>
+__global__ void __launch_bounds__(kVecTpb) batch_exact_kernel(BatchVecArgs<T> a) {
+  __shared__ double s_red[kVecTpb / 64];
+  const int p = a.sl.act[blockIdx.y];
+  const bool is_x = static_cast<int>(blockIdx.x) < a.bx;
+  const int blk = is_x ? blockIdx.x : blockIdx.x - a.bx;
+  double acc[1] = {0.0};
+  const int e = blk * kVecTpb + threadIdx.x;
+  if (is_x && e < a.n) {
+    const size_t o = static_cast<size_t>(p) * a.ldx + e;
+    const T v = a.zx[o] + a.x12[o] + a.zs[p] * a.xt[o] - a.x_cur[o];
+    dev::prod_acc(acc[0], v, v);
+  } else if (!is_x && e < a.m) {
+    const size_t o = static_cast<size_t>(p) * a.ldy + e;
+    const T r = a.zy[o] - a.y12[o];
+    dev::prod_acc(acc[0], r, r);
+  }
+  dev::block_sum<1, kVecTpb>(acc, s_red);
+  if (threadIdx.x == 0) a.part[static_cast<size_t>(p) * (a.bx + a.by) + blockIdx.x] = acc[0];
+}
+
+__global__ void __launch_bounds__(256) batch_sum_kernel(BatchSumJobs jobs, BatchSlots sl, double *out) {
+  __shared__ double s_red[3 * 4];
+  const BatchSumJob jb = jobs.j[blockIdx.x];
+  const int p = sl.act[blockIdx.y];
+  double acc[3] = {0.0, 0.0, 0.0};
+  const double *src = jb.part + static_cast<size_t>(p) * jb.nblk * jb.ns;
+  for (int b = jb.b0 + static_cast<int>(threadIdx.x); b < jb.b1; b += 256)
+#pragma unroll
+    for (int q = 0; q < 3; ++q)
+      if (q < jb.ns) acc[q] += src[static_cast<size_t>(b) * jb.ns + q];
+  dev::block_sum<3, 256>(acc, s_red);
+  if (threadIdx.x == 0)
+#pragma unroll
+    for (int q = 0; q < 3; ++q)
+      if (q < jb.ns) out[static_cast<size_t>(p) * kBatchRec + jb.slot + q] = acc[q];
+}
+
+
+}  // namespace
+
+template <typename T>
+void launch_batch_rows(int tri, const T *M, size_t ldm, int rows, int cols, int cols_pad, const T *X, size_t ldx, T *Y,
+                       size_t ldy, const BatchSlots &sl, hipStream_t s) {
+  const dim3 grid((rows + kBRowsPerWg - 1) / kBRowsPerWg);
+  if (tri == kLower) hipLaunchKernelGGL((batch_rows_kernel<T, kLower>), grid, dim3(256), 0, s, M, ldm, rows, cols, cols_pad, X, ldx, Y, ldy, sl);
+  else if (tri == kUpper) hipLaunchKernelGGL((batch_rows_kernel<T, kUpper>), grid, dim3(256), 0, s, M, ldm, rows, cols, cols_pad, X, ldx, Y, ldy, sl);
+  else hipLaunchKernelGGL((batch_rows_kernel<T, kFull>), grid, dim3(256), 0, s, M, ldm, rows, cols, cols_pad, X, ldx, Y, ldy, sl);
+}
+
+template <typename T>
+void launch_batch_cols(const T *M, size_t ldm, int rows, int cols_pad, int rows_per_block, int nrb, const T *U,
+                       size_t ldu, T *part, int kb, const BatchSlots &sl, hipStream_t s) {
+  constexpr int SLAB = 16 * Vec16<T>::N;
+  static_assert(SLAB == batch_cols_slab<T>(), "slab width");
+  hipLaunchKernelGGL(batch_cols_kernel<T>, dim3((cols_pad + SLAB - 1) / SLAB, nrb), dim3(256), 0, s, M, ldm, rows,
+                     cols_pad, rows_per_block, U, ldu, part, kb, sl);
+}
+
+template <typename T>
+void launch_batch_cols_reduce(const T *part, int nrb, int kb, int cols, int cols_pad, const T *add, T *Z, size_t ldz,
+                              const BatchSlots &sl, hipStream_t s) {
+  hipLaunchKernelGGL(batch_cols_reduce_kernel<T>, dim3((cols_pad + 255) / 256, sl.nact), dim3(256), 0, s, part, nrb, kb,
+                     cols, cols_pad, add, Z, ldz, sl);
+}
+
+template <typename T>
+void launch_batch_pre(const BatchVecArgs<T> &a, hipStream_t s) {
+  hipLaunchKernelGGL(batch_pre_kernel<T>, dim3(a.bx + a.by, a.sl.nact), dim3(kVecTpb), 0, s, a);
+}
+template <typename T>
+void launch_batch_tail(const BatchVecArgs<T> &a, hipStream_t s) {
+  hipLaunchKernelGGL(batch_tail_kernel<T>, dim3(a.bx + a.by, a.sl.nact), dim3(kVecTpb), 0, s, a);
+}
+template <typename T>
+void launch_batch_exact_u(const BatchVecArgs<T> &a, hipStream_t s) {
+  hipLaunchKernelGGL(batch_exact_u_kernel<T>, dim3(a.by, a.sl.nact), dim3(kVecTpb), 0, s, a);
+}
+template <typename T>
+void launch_batch_exact(const BatchVecArgs<T> &a, hipStream_t s) {
+  hipLaunchKernelGGL(batch_exact_kernel<T>, dim3(a.bx + a.by, a.sl.nact), dim3(kVecTpb), 0, s, a);
+}
+void launch_batch_sums(const BatchSumJobs &jobs, int njobs, const BatchSlots &sl, double *out, hipStream_t s) {
+  hipLaunchKernelGGL(batch_sum_kernel, dim3(njobs, sl.nact), dim3(256), 0, s, jobs, sl, out);
+}
+
+#define POGS_BATCH_INST(T)                                                                                             \
+  template void launch_batch_rows<T>(int, const T *, size_t, int, int, int, const T *, size_t, T *, size_t,             \
+                                     const BatchSlots &, hipStream_t);                                                   \
+  template void launch_batch_cols<T>(const T *, size_t, int, int, int, int, const T *, size_t, T *, int,                \
+                                     const BatchSlots &, hipStream_t);                                                   \
+  template void launch_batch_cols_reduce<T>(const T *, int, int, int, int, const T *, T *, size_t, const BatchSlots &,  \
+                                            hipStream_t);                                                                \
+  template void launch_batch_pre<T>(const BatchVecArgs<T> &, hipStream_t);                                             \
+  template void launch_batch_tail<T>(const BatchVecArgs<T> &, hipStream_t);                                            \
+  template void launch_batch_exact_u<T>(const BatchVecArgs<T> &, hipStream_t);                                         \
+  template void launch_batch_exact<T>(const BatchVecArgs<T> &, hipStream_t);
+POGS_BATCH_INST(float)
+POGS_BATCH_INST(double)
+
+}  // namespace pogs_amd

@@ -14,6 +14,7 @@
 // columns zero); x-sized vectors have n_pad entries with zero padding;
 // W = inv(chol(A^T A + I)) lower-triangular and U = W^T, both n x n_pad.
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -21,6 +22,7 @@
 #include <limits>
 #include <thread>
 
+#include "batch_kernels.h"
 #include "cg_kernels.h"
 #include "engine.h"
 #include "fused_cols.h"
@@ -210,6 +212,11 @@ class DenseSolver final : public SolverBase {
     apply_warm_start();
     ctx_.sync();
   }
+
+  // Batched solves (dense_batch.h): separate buffers; the solo state, a pending warm start and the stats of the last
+  // solo solve stay as they are (except iterations, matvecs and reserved[4..7]).
+  void solve_batch(int k, const FnHost *f, const FnHost *g, const double *rho, const SolveParams &p,
+                   const BatchOut &out) override;
 
   void set_warm_start(const void *x0, const void *l0) override {
     warm_x_.assign(static_cast<const T *>(x0), static_cast<const T *>(x0) + n_);
@@ -571,6 +578,7 @@ class DenseSolver final : public SolverBase {
 #include "dense_factor.h"
 #include "dense_iter.h"
 #include "dense_wide.h"
+#include "dense_batch.h"
 
 }  // namespace
 

@@ -635,6 +635,14 @@ inline unsigned warn_negative_coeffs(const FnHost &f, size_t count) {
   return nc + ne;
 }
 
+// Outputs of a batched solve (PogsAmdSolveBatchFn): HOST arrays, problem j at offset j n (x, mu) / j m (y, l) / j.
+struct BatchOut {
+  void *x, *y, *l, *mu;
+  double *optval;
+  unsigned *final_iter;
+  int *status;
+};
+
 // Type-erased solver behind the C handle.
 struct SolverBase {
   virtual ~SolverBase() {}
@@ -643,6 +651,10 @@ struct SolverBase {
   virtual int solve(const FnHost &f, const FnHost &g, const SolveParams &p, void *x, void *y, void *l,
                     void *mu, double *optval, unsigned *final_iter) = 0;
   virtual void begin_run(const FnHost &f, const FnHost &g, const SolveParams &p) = 0;
+  // k problems on the handle's matrix (dense, m > n, direct projector, one GPU); rho: k values or null
+  virtual void solve_batch(int, const FnHost *, const FnHost *, const double *, const SolveParams &, const BatchOut &) {
+    throw Error("batched solves need a dense handle");
+  }
   virtual void iterate(unsigned iters, double *seconds, unsigned *solves) = 0;
   virtual void set_warm_start(const void *x0, const void *l0) = 0;
   virtual void get_equil(void *A_eq, void *d, void *e, double *nrmA) = 0;

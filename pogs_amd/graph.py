@@ -293,6 +293,30 @@ def solve_lasso(A, b, lambd, abs_tol=1e-4, rel_tol=1e-4, max_iter=2500, verbose=
     return _solve_graph_form(A, f, g, abs_tol, rel_tol, max_iter, verbose, rho, dtype=dtype)
 
 
+def _solve_path(A, b, lambdas, make_fg, abs_tol, rel_tol, max_iter, verbose, rho, dtype):
+    lambdas = [float(v) for v in np.atleast_1d(lambdas)]
+    m, n = _shape(A)
+    pairs = [make_fg(b, lam, n) for lam in lambdas]
+    with Solver(A, dtype=dtype) as s:
+        res = s.solve_batch([p[0] for p in pairs], [p[1] for p in pairs], rho=rho, abs_tol=abs_tol, rel_tol=rel_tol,
+                            max_iter=max_iter, verbose=verbose)
+    return {"x": np.stack([r["x"] for r in res]) if res else np.zeros((0, n), _resolve_dtype(dtype)),
+            "optval": np.array([r["optval"] for r in res]),
+            "iterations": np.array([r["iterations"] for r in res], dtype=np.int64),
+            "status": np.array([r["status"] for r in res], dtype=np.int64)}
+
+
+def solve_lasso_path(A, b, lambdas, abs_tol=1e-4, rel_tol=1e-4, max_iter=2500, verbose=0, rho=1.0, dtype=None):
+    """The lasso for every lambda of `lambdas` on one matrix, as batched solves (Solver.solve_batch).
+    Returns {'x': K x n, 'optval', 'iterations', 'status': length K}."""
+    return _solve_path(A, b, lambdas, lasso_functions, abs_tol, rel_tol, max_iter, verbose, rho, dtype)
+
+
+def solve_logistic_path(A, b, lambdas, abs_tol=1e-4, rel_tol=1e-4, max_iter=2500, verbose=0, rho=1.0, dtype=None):
+    """L1-regularised logistic regression for every lambda of `lambdas`, as batched solves (see solve_lasso_path)."""
+    return _solve_path(A, b, lambdas, logistic_functions, abs_tol, rel_tol, max_iter, verbose, rho, dtype)
+
+
 def solve_ridge(A, b, lambd, abs_tol=1e-4, rel_tol=1e-4, max_iter=2500, verbose=0, rho=1.0, dtype=None):
     """minimize 0.5 ||A x - b||^2 + 0.5 lambda ||x||^2   (reference: graph.py:436-476)"""
     m, n = _shape(A)
@@ -464,6 +488,56 @@ class Solver:
             raise RuntimeError("pogs_amd: solve failed: " + _lib.last_error())
         return {"x": x, "y": y, "l": l, "mu": mu, "optval": optval.value, "iterations": final_iter.value,
                 "status": status}
+
+    def solve_batch(self, fs, gs, rho=1.0, abs_tol=1e-4, rel_tol=1e-4, max_iter=2500, verbose=0, adaptive_rho=True,
+                    gap_stop=True):
+        """Solve len(fs) problems (f_j, g_j, rho_j) on this handle's matrix, every pass over A shared by up to
+        BATCH_MAX of them (include/pogs_amd.h: PogsAmdSolveBatchFn; dense, m > n, direct projector, one GPU).
+        ``rho``: one value for all or a sequence.  Longer lists run as consecutive batches.  Returns a list of
+        dicts with the keys `solve` returns.  The handle's solo state (a pending warm start included) is kept."""
+        fs, gs = list(fs), list(gs)
+        k = len(fs)
+        if len(gs) != k:
+            raise ValueError("solve_batch: %d f and %d g function vectors" % (k, len(gs)))
+        if np.ndim(rho) == 0:
+            rhos = [float(rho)] * k
+        else:
+            rhos = [float(r) for r in rho]
+            if len(rhos) != k:
+                raise ValueError("solve_batch: %d problems and %d rho values" % (k, len(rhos)))
+        for f, g in zip(fs, gs):
+            if len(f) != self.m or len(g) != self.n:
+                raise ValueError("solve_batch: f must have length %d and g length %d, got %d and %d"
+                                 % (self.m, self.n, len(f), len(g)))
+        out = []
+        for lo in range(0, k, _lib.BATCH_MAX):
+            hi = min(k, lo + _lib.BATCH_MAX)
+            kb = hi - lo
+            fa = (_lib.PogsAmdFn * kb)()
+            ga = (_lib.PogsAmdFn * kb)()
+            keep = []
+            for j in range(kb):
+                (fst, gst), kp = self._coef(fs[lo + j], gs[lo + j])
+                fa[j], ga[j] = fst, gst
+                keep.append(kp)
+            r = np.ascontiguousarray(rhos[lo:hi], dtype=np.float64)
+            x = np.zeros((kb, self.n), self.dtype)
+            y = np.zeros((kb, self.m), self.dtype)
+            l = np.zeros((kb, self.m), self.dtype)
+            mu = np.zeros((kb, self.n), self.dtype)
+            optval = np.zeros(kb, np.float64)
+            final_iter = np.zeros(kb, np.uint32)
+            status = np.zeros(kb, np.int32)
+            st = lib.PogsAmdSolveBatchFn(self._h, kb, fa, ga, _ptr(r), abs_tol, rel_tol, int(max_iter), int(verbose),
+                                         int(adaptive_rho), int(gap_stop), _ptr(x), _ptr(y), _ptr(l), _ptr(mu),
+                                         _ptr(optval), _ptr(final_iter), _ptr(status))
+            del keep
+            if st != 0:
+                raise RuntimeError("pogs_amd: batched solve failed: " + _lib.last_error())
+            for j in range(kb):
+                out.append({"x": x[j], "y": y[j], "l": l[j], "mu": mu[j], "optval": float(optval[j]),
+                            "iterations": int(final_iter[j]), "status": int(status[j])})
+        return out
 
     def begin_run(self, f, g, abs_tol=1e-4, rel_tol=1e-4, max_iter=2500, rho=1.0, adaptive_rho=True, gap_stop=True):
         args, keep = self._coef(f, g)
