@@ -227,6 +227,34 @@ int PogsAmdSolveBatchFn(PogsAmdSolver *s, int k, const PogsAmdFn *f, const PogsA
                         int adaptive_rho, int gap_stop, void *x, void *y, void *l, void *mu,
                         double *optval, unsigned int *final_iter, int *status);
 
+/* Many small problems, each with its own matrix: k independent graph-form problems, problem j with its own
+ * m x n matrix A_j and its own f[j], g[j], rho[j].  Each one is solved exactly as the one-shot PogsD / PogsS call
+ * solves it: cold start, equilibration, norm estimate, direct projector (m > n factors I + A^T A, m <= n factors
+ * I + A A^T), the reference's stopping rule and adaptive rho.  The whole solve of a problem runs on the device, one
+ * workgroup per problem; a problem's outputs do not depend on k, on its position, on the other problems or on how
+ * the call was split into chunks.
+ * A: the k matrices back to back, matrix j at element offset j*m*n, each in `ord`.  Host or device memory (mem),
+ *    dtype POGS_AMD_F32 / F64.  A device-resident A is never written.
+ * opt: only opt->device and opt->projector are read (NULL = current device, direct projector).  CGLS is refused.
+ * rho: k values, or NULL (1.0 each).  Tolerances, max_iter, adaptive_rho and gap_stop are shared.
+ * Outputs are HOST arrays, laid out as in PogsAmdSolveBatchFn: problem j at offset j*n (x, mu) / j*m (y, l) /
+ *    j (optval, final_iter, status).  y, l, mu, optval may be NULL.
+ * Envelope: 1 <= min(m, n) <= POGS_AMD_MANY_MIN_DIM_MAX and max(m, n) <= POGS_AMD_MANY_MAX_DIM_MAX; any k >= 1.
+ * Memory: the problems run in chunks whose device workspace (equilibrated A_j, W_j = L_j^-1, work vectors) stays
+ *    under POGS_AMD_MANY_WORKSPACE_MB (environment, read at every call; default 1/8 of the device's memory; a
+ *    chunk holds at least one problem).  A host A is uploaded chunk by chunk.
+ * verbose > 0 prints ONE summary for the call (per-iteration lines mean nothing across k problems): k, the count
+ *    of problems per status, the range of iterations, setup and loop time, launches.
+ * Returns 0 when the problems ran (status[j] holds each PogsStatus).  Returns POGS_ERROR when refused:
+ *    PogsAmdLastError says why, and no output has been written. */
+#define POGS_AMD_MANY_MIN_DIM_MAX 512
+#define POGS_AMD_MANY_MAX_DIM_MAX 16384
+int PogsAmdSolveManyFn(int dtype, enum ORD ord, int k, size_t m, size_t n, const void *A, int mem,
+                       const PogsAmdOptions *opt, const PogsAmdFn *f, const PogsAmdFn *g, const double *rho,
+                       double abs_tol, double rel_tol, unsigned int max_iter, unsigned int verbose,
+                       int adaptive_rho, int gap_stop, void *x, void *y, void *l, void *mu,
+                       double *optval, unsigned int *final_iter, int *status);
+
 /* Benchmark stepping.  PogsAmdBeginRun loads f/g and the solve parameters and
  * resets the ADMM state to the cold start; PogsAmdIterate then advances exactly
  * `iters` ADMM iterations of real solves (restarting from the cold start each

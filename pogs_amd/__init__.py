@@ -20,6 +20,7 @@ from .graph import (  # noqa: F401
     solve_huber,
     solve_lasso,
     solve_lasso_path,
+    solve_many,
     solve_logistic,
     solve_logistic_path,
     solve_nonneg_ls,
@@ -32,5 +33,5 @@ from .cvxpy import pogs_solve  # noqa: E402,F401  (reference: python/pogs/__init
 __version__ = "0.1.0"
 __all__ = [
     "solve_lasso", "solve_ridge", "solve_elastic_net", "solve_logistic", "solve_svm", "solve_huber",
-    "solve_nonneg_ls", "solve_lasso_path", "solve_logistic_path", "pogs_solve", "Function", "FunctionObj", "FunctionVector", "Ordering", "Solver",
+    "solve_nonneg_ls", "solve_lasso_path", "solve_logistic_path", "solve_many", "pogs_solve", "Function", "FunctionObj", "FunctionVector", "Ordering", "Solver",
 ]

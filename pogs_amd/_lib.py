@@ -126,6 +126,12 @@ lib.PogsAmdSolveBatchFn.argtypes = [c_void_p, c_int, ctypes.POINTER(PogsAmdFn), 
                                     c_double, c_double, c_uint, c_uint, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_void_p, c_void_p, c_void_p]
 BATCH_MAX = 16   # include/pogs_amd.h: POGS_AMD_BATCH_MAX
+lib.PogsAmdSolveManyFn.argtypes = [c_int, c_int, c_int, c_size_t, c_size_t, c_void_p, c_int, ctypes.POINTER(PogsAmdOptions),
+                                   ctypes.POINTER(PogsAmdFn), ctypes.POINTER(PogsAmdFn), c_void_p, c_double, c_double,
+                                   c_uint, c_uint, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_void_p]
+MANY_MIN_DIM_MAX = 512     # include/pogs_amd.h: POGS_AMD_MANY_MIN_DIM_MAX
+MANY_MAX_DIM_MAX = 16384   # include/pogs_amd.h: POGS_AMD_MANY_MAX_DIM_MAX
 lib.PogsAmdBeginRunFn.argtypes = [c_void_p, ctypes.POINTER(PogsAmdFn), ctypes.POINTER(PogsAmdFn), c_double, c_double, c_double,
                                   c_uint, c_int, c_int]
 lib.PogsAmdBeginRun.argtypes = [c_void_p] + [c_void_p] * 12 + [c_double, c_double, c_double, c_uint, c_int, c_int]
@@ -175,7 +181,7 @@ def pool_trim(device=-1):
 # Every symbol include/pogs_amd.h declares (checked by tests/test_abi.py).
 ABI_SYMBOLS = [
     "PogsD", "PogsS", "PogsSparseD", "PogsSparseS",
-    "PogsAmdDistUniqueId", "PogsAmdCreateDense", "PogsAmdCreateSparse", "PogsAmdSolve", "PogsAmdSolveFn", "PogsAmdSolveBatchFn", "PogsAmdBeginRun", "PogsAmdBeginRunFn",
+    "PogsAmdDistUniqueId", "PogsAmdCreateDense", "PogsAmdCreateSparse", "PogsAmdSolve", "PogsAmdSolveFn", "PogsAmdSolveBatchFn", "PogsAmdSolveManyFn", "PogsAmdBeginRun", "PogsAmdBeginRunFn",
     "PogsAmdIterate", "PogsAmdSetWarmStart", "PogsAmdGetStats", "PogsAmdResetStats", "PogsAmdDestroy", "PogsAmdLastError",
     "PogsAmdPoolStats", "PogsAmdPoolTrim",
     "PogsAmdProxEval", "PogsAmdFuncEval", "PogsAmdProjSubgradEval", "PogsAmdGetEquil", "PogsAmdProject", "PogsAmdMul", "PogsAmdRandUniform",

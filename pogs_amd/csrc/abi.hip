@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "engine.h"
+#include "many_kernels.h"
 #include "prox.h"
 #include "stream.h"
 #include "vec_kernels.h"
@@ -362,6 +363,32 @@ int PogsAmdSolveBatchFn(PogsAmdSolver *s, int k, const PogsAmdFn *f, const PogsA
                          BatchOut{x, y, l, mu, optval, final_iter, status});
     return 0;
   }, s);
+}
+
+int PogsAmdSolveManyFn(int dtype, enum ORD ord, int k, size_t m, size_t n, const void *A, int mem,
+                       const PogsAmdOptions *opt, const PogsAmdFn *f, const PogsAmdFn *g, const double *rho,
+                       double abs_tol, double rel_tol, unsigned int max_iter, unsigned int verbose, int adaptive_rho,
+                       int gap_stop, void *x, void *y, void *l, void *mu, double *optval, unsigned int *final_iter,
+                       int *status) {
+  return guarded([&]() {
+    POGS_CHECK(k >= 1, "many-problem solve: k must be >= 1");
+    POGS_CHECK(f && g, "many-problem solve: null function descriptions");
+    POGS_CHECK(x && final_iter && status, "many-problem solve: x, final_iter and status must not be NULL");
+    const int projector = opt ? opt->projector : POGS_AMD_PROJ_DEFAULT;
+    POGS_CHECK(projector == POGS_AMD_PROJ_DEFAULT || projector == POGS_AMD_PROJ_DIRECT,
+               "many-problem solve: only the direct projector is supported (CGLS refused)");
+    const int device = opt ? opt->device : -1;
+    DeviceGuard guard(device);
+    std::vector<FnHost> fh, gh;
+    for (int j = 0; j < k; ++j) {
+      fh.push_back(fn_host(&f[j]));
+      gh.push_back(fn_host(&g[j]));
+    }
+    solve_many(dtype, static_cast<int>(ord), k, m, n, A, mem, device, fh.data(), gh.data(), rho,
+               make_params(1.0, abs_tol, rel_tol, max_iter, verbose, adaptive_rho, gap_stop),
+               BatchOut{x, y, l, mu, optval, final_iter, status});
+    return 0;
+  });
 }
 
 int PogsAmdBeginRunFn(PogsAmdSolver *s, const PogsAmdFn *f, const PogsAmdFn *g, double rho, double abs_tol, double rel_tol,

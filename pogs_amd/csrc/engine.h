@@ -361,7 +361,26 @@ struct Ctx {
   }
 };
 
-// Host-side scalar logic of PogsImplementation::Solve for a separable objective
+// AdmmControl below runs on the host (every solver's loop) and on the device (the many-problem loop,
+// many_kernels.hip): the same arithmetic in both places.  The reference's rho messages (verbose > 3)
+// are the host's business.
+#define POGS_HD __host__ __device__
+#if defined(__HIP_DEVICE_COMPILE__)
+#define POGS_SAY_RHO(fmt, ...) ((void)0)
+#else
+#define POGS_SAY_RHO(fmt, ...) do { if (say_rho) std::printf(fmt, __VA_ARGS__); } while (0)
+#endif
+POGS_HD inline float ctl_abs(float v) { return fabsf(v); }
+POGS_HD inline double ctl_abs(double v) { return fabs(v); }
+POGS_HD inline float ctl_sqrt(float v) { return sqrtf(v); }
+POGS_HD inline double ctl_sqrt(double v) { return sqrt(v); }
+POGS_HD inline float ctl_pow(float a, float b) { return powf(a, b); }
+POGS_HD inline double ctl_pow(double a, double b) { return pow(a, b); }
+// (std::min / std::max's exact comparisons)
+template <typename T> POGS_HD inline T ctl_min(T a, T b) { return b < a ? b : a; }
+template <typename T> POGS_HD inline T ctl_max(T a, T b) { return a < b ? b : a; }
+
+// Scalar logic of PogsImplementation::Solve for a separable objective
 // (kUseExactTol = false): constants pogs.cpp:94-110, tolerances :199-201,270-273,
 // projection tolerance :287-290, stopping rule :379-394, adaptive rho :402-466.
 // Arithmetic is carried out in T exactly where the reference uses T.
@@ -384,7 +403,7 @@ struct AdmmControl {
   T sqrtn_atol = 0, sqrtm_atol = 0, sqrtmn_atol = 0;
 
   static constexpr double kAlphaD = 1.7;
-  T alpha() const { return static_cast<T>(kAlphaD); }
+  POGS_HD T alpha() const { return static_cast<T>(kAlphaD); }
 
   void reset() {
     rho = rho0;
@@ -400,34 +419,34 @@ struct AdmmControl {
   }
 
   // After the prox step: S holds the pre-projection sums.
-  void set_pre(const double *S) {
-    gap = std::abs(static_cast<T>(S[kGapX] + S[kGapY]));
-    const T nz = static_cast<T>(std::sqrt(S[kWX2] + S[kWY2]));
-    const T nz12 = static_cast<T>(std::sqrt(S[kHX2] + S[kHY2]));
-    const T ny12 = static_cast<T>(std::sqrt(S[kHY2]));
-    const T nx = static_cast<T>(std::sqrt(S[kWX2]));
+  POGS_HD void set_pre(const double *S) {
+    gap = ctl_abs(static_cast<T>(S[kGapX] + S[kGapY]));
+    const T nz = static_cast<T>(ctl_sqrt(S[kWX2] + S[kWY2]));
+    const T nz12 = static_cast<T>(ctl_sqrt(S[kHX2] + S[kHY2]));
+    const T ny12 = static_cast<T>(ctl_sqrt(S[kHY2]));
+    const T nx = static_cast<T>(ctl_sqrt(S[kWX2]));
     eps_gap = sqrtmn_atol + rel_tol * nz * nz12;
     eps_pri = sqrtm_atol + rel_tol * ny12;
     eps_dua = rho * (sqrtn_atol + rel_tol * nx);
   }
-  T proj_tol() const {
-    T tol = static_cast<T>(1e-2) * std::pow(std::min(prev_nrm_r, static_cast<T>(1)), static_cast<T>(0.5));
-    return std::max(tol, static_cast<T>(1e-8));
+  POGS_HD T proj_tol() const {
+    T tol = static_cast<T>(1e-2) * ctl_pow(ctl_min(prev_nrm_r, static_cast<T>(1)), static_cast<T>(0.5));
+    return ctl_max(tol, static_cast<T>(1e-8));
   }
   // After the projection: cheap residual bounds; returns whether the exact
   // residuals must be evaluated.
-  bool set_approx(const double *S, T nrmA) {
-    nrm_s = rho * (nrmA * static_cast<T>(std::sqrt(S[kDYprev2])) + static_cast<T>(std::sqrt(S[kDXprev2])));
-    nrm_r = nrmA * static_cast<T>(std::sqrt(S[kDX12])) + static_cast<T>(std::sqrt(S[kDY12]));
+  POGS_HD bool set_approx(const double *S, T nrmA) {
+    nrm_s = rho * (nrmA * static_cast<T>(ctl_sqrt(S[kDYprev2])) + static_cast<T>(ctl_sqrt(S[kDXprev2])));
+    nrm_r = nrmA * static_cast<T>(ctl_sqrt(S[kDX12])) + static_cast<T>(ctl_sqrt(S[kDY12]));
     return nrm_r < 10 * eps_pri && nrm_s < 10 * eps_dua;
   }
-  void set_exact(const double *S) {
-    nrm_r = static_cast<T>(std::sqrt(S[kExactR2]));
-    nrm_s = rho * static_cast<T>(std::sqrt(S[kExactS2]));
+  POGS_HD void set_exact(const double *S) {
+    nrm_r = static_cast<T>(ctl_sqrt(S[kExactR2]));
+    nrm_s = rho * static_cast<T>(ctl_sqrt(S[kExactS2]));
     ++exact_iters;
   }
   // Returns true when the solve stops at this iteration (k is then final_iter).
-  bool check_stop(bool exact) {
+  POGS_HD bool check_stop(bool exact) {
     converged = exact && nrm_r < eps_pri && nrm_s < eps_dua && (!gap_stop || gap < eps_gap);
     if (converged || k == max_iter - 1) {
       finished = true;
@@ -436,7 +455,7 @@ struct AdmmControl {
     return false;
   }
   // Adaptive rho; returns the factor zt must be multiplied by (1 = unchanged).
-  T adapt() {
+  POGS_HD T adapt() {
     T scale = 1;
     const T kDeltaMin = static_cast<T>(1.05), kGamma = static_cast<T>(1.01), kTau = static_cast<T>(0.8);
     const T kRhoMin = static_cast<T>(1e-4), kRhoMax = static_cast<T>(1e4), kKappa = static_cast<T>(0.9);
@@ -450,15 +469,15 @@ struct AdmmControl {
         if (pri_n > kZero && dua_n > kZero) {
           const T imbalance = pri_n / dua_n;
           if (imbalance > kImbalanceThresh || imbalance < kOne / kImbalanceThresh) {
-            T ratio = std::sqrt(imbalance);
-            ratio = std::max(kRhoChangeMin, std::min(kRhoChangeMax, ratio));
+            T ratio = ctl_sqrt(imbalance);
+            ratio = ctl_max(kRhoChangeMin, ctl_min(kRhoChangeMax, ratio));
             T rho_new = rho * ratio;
-            rho_new = std::max(kRhoMin, std::min(kRhoMax, rho_new));
-            if (std::abs(rho_new - rho) / rho > static_cast<T>(0.05)) {
+            rho_new = ctl_max(kRhoMin, ctl_min(kRhoMax, rho_new));
+            if (ctl_abs(rho_new - rho) / rho > static_cast<T>(0.05)) {
               scale = rho / rho_new;
               rho = rho_new;
               ++rho_updates;
-              if (say_rho) std::printf("spectral rho update: %e (imbalance=%.1f)\n", (double)rho, (double)imbalance);
+              POGS_SAY_RHO("spectral rho update: %e (imbalance=%.1f)\n", (double)rho, (double)imbalance);
             }
           }
         }
@@ -469,7 +488,7 @@ struct AdmmControl {
           delta = kGamma * delta;
           ku = k;
           ++rho_updates;
-          if (say_rho) std::printf("+ rho %e\n", (double)rho);
+          POGS_SAY_RHO("+ rho %e\n", (double)rho);
         }
       } else if (nrm_s > xi * eps_dua && nrm_r < xi * eps_pri && kTau * static_cast<T>(k) > static_cast<T>(ku)) {
         if (rho > kRhoMin) {
@@ -478,7 +497,7 @@ struct AdmmControl {
           delta = kGamma * delta;
           kd = k;
           ++rho_updates;
-          if (say_rho) std::printf("- rho %e\n", (double)rho);
+          POGS_SAY_RHO("- rho %e\n", (double)rho);
         }
       } else if (nrm_s < xi * eps_dua && nrm_r < xi * eps_pri) {
         xi *= kKappa;
@@ -492,13 +511,13 @@ struct AdmmControl {
   // What adapt() would do at this iteration if the residuals equalled the previous
   // iteration's (they drift slowly): returns the predicted (rho, zt scale) without
   // touching the state.  Used to speculate across a rho change (dense_solver.h).
-  void predict(T *rho_out, T *scale_out) const {
+  POGS_HD void predict(T *rho_out, T *scale_out) const {
     AdmmControl<T> c = *this;   // nrm_r, nrm_s, eps_* still hold the previous iteration's values
     c.say_rho = false;
     *scale_out = c.adapt();
     *rho_out = c.rho;
   }
-  int status() const {
+  POGS_HD int status() const {
     if (!converged && k == max_iter - 1) return POGS_MAX_ITER;
     if (!converged) return POGS_NAN_FOUND;
     return POGS_SUCCESS;

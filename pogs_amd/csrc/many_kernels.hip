@@ -1,0 +1,760 @@
+// Many small dense problems, each with its own matrix (PogsAmdSolveManyFn, include/pogs_amd.h).
+//
+// One workgroup owns one problem from setup to epilogue: it copies and equilibrates its A_j, estimates its norm,
+// factors I + A^T A (m > n) or I + A A^T (m <= n), inverts the Cholesky factor (W = L^-1), and runs the two-pass
+// ADMM iteration of pogs.cpp with the stopping rule and adaptive rho of AdmmControl (engine.h) on the device.  Only
+// the Gram matrix is formed by several workgroups per problem (one 64 x 64 tile each).  Problems never talk to each
+// other, so there is no host poll per iteration: a loop launch advances every live problem by at most a fixed number
+// of iterations, keeps its state in device memory, and the host reads back one done-count per launch.
+//
+// Every sum inside a problem runs in a fixed order that depends on (m, n) alone (fixed thread -> element maps,
+// fixed butterflies, partials combined in index order), and a problem's arithmetic never looks at its index, the
+// chunk or the other problems: its bytes are its own.
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <vector>
+
+#include "many_kernels.h"
+#include "prox.h"
+#include "reduce.h"
+
+namespace pogs_amd {
+
+void rand_uniform_host(float *x, size_t n);    // abi.hip: the Norm2Est start vector (gsl_rand.h:8-16)
+void rand_uniform_host(double *x, size_t n);
+
+namespace {
+
+constexpr int kTPB = 256;
+constexpr int kWaves = kTPB / 64;
+constexpr int kMaxIterPerLaunch = 64;
+// Work of one workgroup in one launch is bounded by about this many bytes streamed (the Sinkhorn-Knopp passes, the
+// power iterations and the ADMM iterations are cut into launches by it), so that no launch runs long at the edge of
+// the envelope (16384 x 512 fp64 = 64 MB per pass over A).
+constexpr double kLaunchBytes = 256.0 * (1 << 20);
+
+// One function vector on the device: a field is an array or one value for every element (PogsAmdFn's broadcast).
+template <typename T>
+struct ManyFn {
+  const T *p[5];   // a, b, c, d, e
+  const int *h;
+  T v[5];
+  int h0;
+  __device__ __forceinline__ T get(int f, int i) const { return p[f] ? p[f][i] : v[f]; }
+  __device__ __forceinline__ int code(int i) const { return h ? h[i] : h0; }
+};
+
+// Per-problem setup scalars.
+template <typename T>
+struct ManyState {
+  T nrmA, ne_est;
+  int ne_iter, ne_done, stopped, pad;
+};
+
+// x-sized and y-sized work vectors of a problem (z = [x | y] of pogs.cpp:129-138, its copies, the scalings)
+enum XVec : int { kX = 0, kXt, kXprev, kX12, kXtemp, kE, kXs, kNumX };
+enum YVec : int { kY = 0, kYt, kYprev, kY12, kYtemp, kD, kYs, kNumY };
+
+template <typename T>
+struct ManyArgs {
+  int m, n, k, tall;
+  size_t stride;                 // elements of T per problem in ws
+  size_t oA, oW, oT, ox[kNumX], oy[kNumY];
+  T *ws;
+  const T *src;                  // the chunk's input matrices, problem q at q*m*n
+  int rowmaj;
+  const T *rnd;                  // Norm2Est start vector (n)
+  const ManyFn<T> *fn;           // f of problem q at 2q, g at 2q + 1
+  AdmmControl<T> *ctl;
+  ManyState<T> *st;
+  unsigned *done_count;
+  T ce, cd;                      // Sinkhorn-Knopp regularisers (equil_helper.h:152-160)
+  T *xo, *yo, *lo, *muo;         // chunk outputs, problem q at q*n / q*m
+  double *optval;
+  unsigned *iters;
+  int *status;
+};
+
+// ---- workgroup building blocks -------------------------------------------------------------------
+
+// NS double sums over the workgroup, the totals in every thread.  red: NS * (kWaves + 1) doubles.
+template <int NS>
+__device__ __forceinline__ void wg_sum(double (&v)[NS], double *red) {
+  dev::block_sum<NS, kTPB>(v, red);
+  if (threadIdx.x == 0)
+    for (int q = 0; q < NS; ++q) red[NS * kWaves + q] = v[q];
+  __syncthreads();
+  for (int q = 0; q < NS; ++q) v[q] = red[NS * kWaves + q];
+  __syncthreads();
+}
+
+// out(i, s), s = sum_{c < len(i)} M[i ld + c] v[c] (SQ: M^2 v) for the rows i < rows: one wavefront per row, lanes over
+// the columns, the lanes' partials summed by the butterfly.  Call from all threads; no barrier inside.
+template <typename T, bool SQ, typename Len, typename Out>
+__device__ __forceinline__ void row_dots(const T *M, size_t ld, int rows, Len len, const T *v, Out out) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  for (int i = w; i < rows; i += kWaves) {
+    const T *r = M + static_cast<size_t>(i) * ld;
+    const int L = len(i);
+    T acc = 0;
+    for (int c = lane; c < L; c += 64) {
+      const T a = r[c];
+      acc += SQ ? (a * a) * v[c] : a * v[c];
+    }
+    acc = dev::wave_sum(acc);
+    if (lane == 0) out(i, acc);
+  }
+}
+
+// out(c, s), s = sum_{r0(c) <= i < rows} M[i ld + c] v[i] (SQ: M^2 v) for the columns c < cols: a thread per column,
+// and for narrow matrices (cols <= 128) 2 or 4 thread groups over interleaved rows whose partials are added in group
+// order.  Call from all threads; ends with the outputs written (not yet visible: the caller syncs).  part: kTPB T.
+template <typename T, bool SQ, typename R0, typename Out>
+__device__ __forceinline__ void col_dots(const T *M, size_t ld, int rows, int cols, R0 r0, const T *v, Out out,
+                                         T *part) {
+  const int CP = cols >= kTPB ? kTPB : (cols + 63) / 64 * 64;
+  const int RG = kTPB / CP;
+  const int t = threadIdx.x, cc = t % CP, rg = t / CP;
+  for (int c0 = 0; c0 < cols; c0 += CP) {
+    const int c = c0 + cc;
+    T acc = 0;
+    if (rg < RG && c < cols) {
+      for (int i = r0(c) + rg; i < rows; i += RG) {
+        const T a = M[static_cast<size_t>(i) * ld + c];
+        acc += SQ ? (a * a) * v[i] : a * v[i];
+      }
+    }
+    if (RG > 1) {
+      part[t] = acc;
+      __syncthreads();
+      if (rg == 0 && c < cols) {
+        T s = part[cc];
+        for (int q = 1; q < RG; ++q) s += part[q * CP + cc];
+        out(c, s);
+      }
+      __syncthreads();
+    } else if (rg == 0 && c < cols) {
+      out(c, acc);
+    }
+  }
+}
+
+// The scaled function of element i (PogsObjectiveSeparable::scale, pogs.cpp:608-617, after FunctionObj's clamp of
+// c and e, prox_lib.h:62-69): f by 1 / d_i (isf), g by e_j.
+template <typename T>
+struct Coef {
+  T a, b, c, d, e;
+  int h;
+};
+template <typename T>
+__device__ __forceinline__ Coef<T> coef(const ManyFn<T> &F, int i, T s, bool isf) {
+  Coef<T> r;
+  r.h = F.code(i);
+  r.a = F.get(0, i); r.b = F.get(1, i); r.c = F.get(2, i); r.d = F.get(3, i); r.e = F.get(4, i);
+  r.c = r.c < static_cast<T>(0) ? static_cast<T>(0) : r.c;
+  r.e = r.e < static_cast<T>(0) ? static_cast<T>(0) : r.e;
+  if (isf) {
+    r.a = r.a / s; r.d = r.d / s; r.e = r.e / (s * s);
+  } else {
+    r.a = r.a * s; r.d = r.d * s; r.e = r.e * (s * s);
+  }
+  return r;
+}
+
+// ---- setup ------------------------------------------------------------------------------------------
+
+// A_j (row- or column-major input) into the problem's row-major copy.  grid (blocks, problems)
+template <typename T>
+__global__ __launch_bounds__(kTPB) void many_copy_kernel(ManyArgs<T> a) {
+  const int q = blockIdx.y;
+  const size_t mn = static_cast<size_t>(a.m) * a.n;
+  const T *src = a.src + q * mn;
+  T *A = a.ws + q * a.stride + a.oA;
+  for (size_t idx = static_cast<size_t>(blockIdx.x) * kTPB + threadIdx.x; idx < mn;
+       idx += static_cast<size_t>(gridDim.x) * kTPB) {
+    const size_t i = idx / a.n, c = idx % a.n;
+    A[idx] = a.rowmaj ? src[idx] : src[c * a.m + i];
+  }
+}
+
+// Sinkhorn-Knopp on A.^2 (equil_helper.h:140-164, all 50 passes), passes [p0, p0 + np) of them.  grid: problems
+template <typename T>
+__global__ __launch_bounds__(kTPB) void many_sk_kernel(ManyArgs<T> a, int p0, int np) {
+  __shared__ T part[kTPB];
+  const int q = blockIdx.x, m = a.m, n = a.n;
+  T *w = a.ws + q * a.stride;
+  const T *A = w + a.oA;
+  T *d = w + a.oy[kD], *e = w + a.ox[kE];
+  if (p0 == 0) {
+    for (int i = threadIdx.x; i < m; i += kTPB) d[i] = 1;
+    __syncthreads();
+  }
+  const T tm = static_cast<T>(m), tn = static_cast<T>(n), ce = a.ce, cd = a.cd;
+  for (int p = p0; p < p0 + np; ++p) {
+    col_dots<T, true>(A, n, m, n, [](int) { return 0; }, d, [&](int c, T s) { e[c] = tm / (s + ce); }, part);
+    __syncthreads();
+    row_dots<T, true>(A, n, m, [&](int) { return n; }, e, [&](int i, T s) { d[i] = tn / (s + cd); });
+    __syncthreads();
+  }
+}
+
+// MatrixDense::Equil's closing steps (matrix_dense.cpp:176-192): d, e <- sqrt; A <- diag(d) A diag(e) (as the
+// sign-bit round trip leaves it, sign(a) sqrt(a^2)); A, d, e normalised by ||A||_F / sqrt(min(m, n)).  grid: problems
+template <typename T>
+__global__ __launch_bounds__(kTPB) void many_scale_kernel(ManyArgs<T> a) {
+  __shared__ double red[1 * (kWaves + 1)];
+  const int q = blockIdx.x, m = a.m, n = a.n;
+  T *w = a.ws + q * a.stride;
+  T *A = w + a.oA, *d = w + a.oy[kD], *e = w + a.ox[kE];
+  for (int i = threadIdx.x; i < m; i += kTPB) d[i] = dev::Sqrt(d[i]);
+  for (int j = threadIdx.x; j < n; j += kTPB) e[j] = dev::Sqrt(e[j]);
+  __syncthreads();
+  const size_t mn = static_cast<size_t>(m) * n;
+  double fro[1] = {0};
+  for (size_t idx = threadIdx.x; idx < mn; idx += kTPB) {
+    const size_t i = idx / n, c = idx % n;
+    const T v0 = A[idx];
+    T v = static_cast<T>(1 - 2 * (v0 < 0)) * dev::Sqrt(v0 * v0);
+    v *= d[i] * e[c];
+    A[idx] = v;
+    fro[0] += static_cast<double>(v) * v;
+  }
+  wg_sum<1>(fro, red);
+  const T normA = static_cast<T>(sqrt(fro[0])) / dev::Sqrt(static_cast<T>(m < n ? m : n));
+  const T inv = static_cast<T>(1) / normA;
+  for (size_t idx = threadIdx.x; idx < mn; idx += kTPB) A[idx] *= inv;
+  const T invs = static_cast<T>(1) / dev::Sqrt(normA);
+  for (int i = threadIdx.x; i < m; i += kTPB) d[i] *= invs;
+  for (int j = threadIdx.x; j < n; j += kTPB) e[j] *= invs;
+}
+
+// Norm2Est (equil_helper.h:107-135) on the equilibrated A: power iterations [it0, it0 + nit), state in ManyState.
+// grid: problems
+template <typename T>
+__global__ __launch_bounds__(kTPB) void many_normest_kernel(ManyArgs<T> a, int it0, int nit) {
+  __shared__ double red[2 * (kWaves + 1)];
+  __shared__ T part[kTPB];
+  const int q = blockIdx.x, m = a.m, n = a.n;
+  ManyState<T> &st = a.st[q];
+  if (it0 > 0 && st.ne_done) return;
+  T *w = a.ws + q * a.stride;
+  const T *A = w + a.oA;
+  T *x = w + a.ox[kXtemp], *Sx = w + a.oy[kYtemp];
+  T est = 0;
+  int it = 0;
+  if (it0 == 0) {
+    for (int j = threadIdx.x; j < n; j += kTPB) x[j] = a.rnd[j];
+    __syncthreads();
+  } else {
+    est = st.ne_est;
+    it = st.ne_iter;
+  }
+  const T kTol = static_cast<T>(1e-4);
+  bool done = false;
+  for (int r = 0; r < nit && it < 50; ++r) {
+    const T last = est;
+    row_dots<T, false>(A, n, m, [&](int) { return n; }, x, [&](int i, T s) { Sx[i] = s; });
+    __syncthreads();
+    col_dots<T, false>(A, n, m, n, [](int) { return 0; }, Sx, [&](int c, T s) { x[c] = s; }, part);
+    __syncthreads();
+    double s2[2] = {0, 0};
+    for (int j = threadIdx.x; j < n; j += kTPB) s2[0] += static_cast<double>(x[j]) * x[j];
+    for (int i = threadIdx.x; i < m; i += kTPB) s2[1] += static_cast<double>(Sx[i]) * Sx[i];
+    wg_sum<2>(s2, red);
+    const T normx = static_cast<T>(sqrt(s2[0])), normSx = static_cast<T>(sqrt(s2[1]));
+    const T sc = static_cast<T>(1) / normx;
+    for (int j = threadIdx.x; j < n; j += kTPB) x[j] *= sc;
+    est = normx / normSx;
+    ++it;
+    __syncthreads();
+    if (dev::Abs(last - est) < kTol * est) { done = true; break; }
+  }
+  if (threadIdx.x == 0) {
+    st.ne_est = est;
+    st.ne_iter = it;
+    st.ne_done = done || it >= 50;
+    st.nrmA = est;
+  }
+}
+
+// Lower triangle of the Gram matrix, A^T A (m > n) or A A^T (m <= n), into W: one 64 x 64 tile per workgroup,
+// 4 x 4 per thread, summed over the long dimension in order.  grid (lower tiles, problems)
+template <typename T>
+__global__ __launch_bounds__(kTPB) void many_gram_kernel(ManyArgs<T> a) {
+  const int q = blockIdx.y, k = a.k, n = a.n;
+  int bi = 0;
+  const int t = blockIdx.x;
+  while ((bi + 1) * (bi + 2) / 2 <= t) ++bi;
+  const int bj = t - bi * (bi + 1) / 2;
+  T *w = a.ws + q * a.stride;
+  const T *A = w + a.oA;
+  T *G = w + a.oW;
+  const int i0 = bi * 64 + (threadIdx.x / 16) * 4, j0 = bj * 64 + (threadIdx.x % 16) * 4;
+  const int R = a.tall ? a.m : a.n;
+  // element (r, i) of the factor whose Gram is formed: A[r][i] (tall) or A[i][r] (wide)
+  const size_t si = a.tall ? 1 : static_cast<size_t>(n), sr = a.tall ? static_cast<size_t>(n) : 1;
+  T acc[4][4] = {};
+  for (int r = 0; r < R; ++r) {
+    T u[4], v[4];
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      u[p] = i0 + p < k ? A[r * sr + (i0 + p) * si] : static_cast<T>(0);
+      v[p] = j0 + p < k ? A[r * sr + (j0 + p) * si] : static_cast<T>(0);
+    }
+#pragma unroll
+    for (int p = 0; p < 4; ++p)
+#pragma unroll
+      for (int s = 0; s < 4; ++s) acc[p][s] += u[p] * v[s];
+  }
+#pragma unroll
+  for (int p = 0; p < 4; ++p)
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+      if (i0 + p < k && j0 + s <= i0 + p) G[static_cast<size_t>(i0 + p) * k + j0 + s] = acc[p][s];
+}
+
+// I + G = L L^T (the left-looking row Cholesky of gsl_linalg.h:12-55, diagonal sums in fp64), then W = L^-1 in place
+// (column by column from the right, as LAPACK's trti2).  Lower triangles only.  grid: problems
+template <typename T>
+__global__ __launch_bounds__(kTPB) void many_factor_kernel(ManyArgs<T> a) {
+  __shared__ T bc;
+  const int q = blockIdx.x, k = a.k;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  T *w = a.ws + q * a.stride;
+  T *L = w + a.oW, *tmp = w + a.oT;
+  for (int j = 0; j < k; ++j) {
+    const T *lj = L + static_cast<size_t>(j) * k;
+    if (wv == 0) {
+      double s = 0;
+      for (int p = lane; p < j; p += 64) s += static_cast<double>(lj[p]) * lj[p];
+      s = dev::wave_sum(s);
+      if (lane == 0) {
+        const double djj = static_cast<double>(static_cast<T>(lj[j] + static_cast<T>(1))) - s;
+        const T ljj = static_cast<T>(sqrt(djj));
+        L[static_cast<size_t>(j) * k + j] = ljj;
+        bc = ljj;
+      }
+    }
+    __syncthreads();
+    const T ljj = bc;
+    for (int i = j + 1 + wv; i < k; i += kWaves) {
+      T *li = L + static_cast<size_t>(i) * k;
+      T acc = 0;
+      for (int p = lane; p < j; p += 64) acc += li[p] * lj[p];
+      acc = dev::wave_sum(acc);
+      if (lane == 0) li[j] = (li[j] - acc) / ljj;
+    }
+    __syncthreads();
+  }
+  for (int j = k - 1; j >= 0; --j) {
+    for (int p = j + 1 + threadIdx.x; p < k; p += kTPB) tmp[p] = L[static_cast<size_t>(p) * k + j];
+    if (threadIdx.x == 0) {
+      const T wjj = static_cast<T>(1) / L[static_cast<size_t>(j) * k + j];
+      L[static_cast<size_t>(j) * k + j] = wjj;
+      bc = -wjj;
+    }
+    __syncthreads();
+    const T ajj = bc;
+    for (int i = j + 1 + wv; i < k; i += kWaves) {
+      const T *wi = L + static_cast<size_t>(i) * k;
+      T acc = 0;
+      for (int p = j + 1 + lane; p <= i; p += 64) acc += wi[p] * tmp[p];
+      acc = dev::wave_sum(acc);
+      if (lane == 0) L[static_cast<size_t>(i) * k + j] = ajj * acc;
+    }
+    __syncthreads();
+  }
+}
+
+// ---- the ADMM loop ----------------------------------------------------------------------------------
+
+// At most `iters` iterations of every live problem (PogsImplementation::Solve, pogs.cpp:252-469, in its order; the
+// direct projector of projector_direct_dense.cpp:87-175 with the factor's inverse), then, for a problem that stops,
+// optval and the un-scaled outputs (pogs.cpp:473-518).  grid: problems
+template <typename T>
+__global__ __launch_bounds__(kTPB) void many_loop_kernel(ManyArgs<T> a, int iters) {
+  __shared__ double red[6 * (kWaves + 1)];
+  __shared__ T part[kTPB];
+  const int q = blockIdx.x, m = a.m, n = a.n, k = a.k;
+  if (a.st[q].stopped) return;
+  T *w = a.ws + q * a.stride;
+  const T *A = w + a.oA, *W = w + a.oW;
+  T *tv = w + a.oT;
+  T *x = w + a.ox[kX], *xt = w + a.ox[kXt], *xprev = w + a.ox[kXprev], *x12 = w + a.ox[kX12];
+  T *xtemp = w + a.ox[kXtemp], *xs = w + a.ox[kXs];
+  const T *e = w + a.ox[kE];
+  T *y = w + a.oy[kY], *yt = w + a.oy[kYt], *yprev = w + a.oy[kYprev], *y12 = w + a.oy[kY12];
+  T *ytemp = w + a.oy[kYtemp], *ys = w + a.oy[kYs];
+  const T *d = w + a.oy[kD];
+  const ManyFn<T> F = a.fn[2 * q], G = a.fn[2 * q + 1];
+  const T nrmA = a.st[q].nrmA;
+  // every thread runs the control on the same (broadcast) sums and makes the same decisions; thread 0 stores it
+  AdmmControl<T> c = a.ctl[q];
+  T rho = c.rho;
+  const T alpha = c.alpha(), oma = static_cast<T>(1) - alpha;
+  double S[kNumSlots];
+  for (int i = 0; i < kNumSlots; ++i) S[i] = 0;
+  auto all_cols = [](int) { return 0; };
+  auto full_row = [&](int) { return n; };
+  for (int it = 0; it < iters; ++it) {
+    // zprev = z; z -= zt; z12 = prox(z); z -= z12; the pre-projection sums (pogs.cpp:254-273)
+    double s6[6] = {0, 0, 0, 0, 0, 0};
+    for (int j = threadIdx.x; j < n; j += kTPB) {
+      const T xp = x[j];
+      xprev[j] = xp;
+      const T v = xp - xt[j];
+      const Coef<T> g = coef(G, j, e[j], false);
+      const T h = dev::ProxEval(g.h, g.a, g.b, g.c, g.d, g.e, v, rho);
+      x12[j] = h;
+      const T r = v - h;
+      x[j] = r;
+      s6[0] += static_cast<double>(r) * h;
+      s6[1] += static_cast<double>(r) * r;
+      s6[2] += static_cast<double>(h) * h;
+    }
+    for (int i = threadIdx.x; i < m; i += kTPB) {
+      const T yp = y[i];
+      yprev[i] = yp;
+      const T v = yp - yt[i];
+      const Coef<T> f = coef(F, i, d[i], true);
+      const T h = dev::ProxEval(f.h, f.a, f.b, f.c, f.d, f.e, v, rho);
+      y12[i] = h;
+      const T r = v - h;
+      y[i] = r;
+      s6[3] += static_cast<double>(r) * h;
+      s6[4] += static_cast<double>(r) * r;
+      s6[5] += static_cast<double>(h) * h;
+    }
+    wg_sum<6>(s6, red);
+    S[kGapX] = s6[0]; S[kWX2] = s6[1]; S[kHX2] = s6[2];
+    S[kGapY] = s6[3]; S[kWY2] = s6[4]; S[kHY2] = s6[5];
+    c.set_pre(S);
+    // ztemp = zt + alpha z12 + (1 - alpha) zprev (pogs.cpp:276-278)
+    for (int j = threadIdx.x; j < n; j += kTPB) xtemp[j] = (xt[j] + alpha * x12[j]) + oma * xprev[j];
+    for (int i = threadIdx.x; i < m; i += kTPB) ytemp[i] = (yt[i] + alpha * y12[i]) + oma * yprev[i];
+    __syncthreads();
+    // projection of ztemp onto y = A x (projector_direct_dense.cpp:122-135), (I + G)^-1 = W^T W
+    if (a.tall) {
+      col_dots<T, false>(A, n, m, n, all_cols, ytemp, [&](int j, T s) { xs[j] = xtemp[j] + s; }, part);
+      __syncthreads();
+      row_dots<T, false>(W, k, k, [](int i) { return i + 1; }, xs, [&](int i, T s) { tv[i] = s; });
+      __syncthreads();
+      col_dots<T, false>(W, k, k, k, [](int j) { return j; }, tv, [&](int j, T s) { x[j] = s; }, part);
+      __syncthreads();
+      row_dots<T, false>(A, n, m, full_row, x, [&](int i, T s) { y[i] = s; });
+      __syncthreads();
+    } else {
+      row_dots<T, false>(A, n, m, full_row, xtemp, [&](int i, T s) { ys[i] = s - ytemp[i]; });
+      __syncthreads();
+      row_dots<T, false>(W, k, k, [](int i) { return i + 1; }, ys, [&](int i, T s) { tv[i] = s; });
+      __syncthreads();
+      col_dots<T, false>(W, k, k, k, [](int j) { return j; }, tv, [&](int j, T s) { ys[j] = s; }, part);
+      __syncthreads();
+      col_dots<T, false>(A, n, m, n, all_cols, ys, [&](int j, T s) { x[j] = xtemp[j] - s; }, part);
+      for (int i = threadIdx.x; i < m; i += kTPB) y[i] = ys[i] + ytemp[i];
+      __syncthreads();
+    }
+    // approximate residuals (pogs.cpp:342-348)
+    double s4[4] = {0, 0, 0, 0};
+    for (int j = threadIdx.x; j < n; j += kTPB) {
+      const T u = xprev[j] - x[j], v = x12[j] - x[j];
+      s4[0] += static_cast<double>(u) * u;
+      s4[1] += static_cast<double>(v) * v;
+    }
+    for (int i = threadIdx.x; i < m; i += kTPB) {
+      const T u = yprev[i] - y[i], v = y12[i] - y[i];
+      s4[2] += static_cast<double>(u) * u;
+      s4[3] += static_cast<double>(v) * v;
+    }
+    wg_sum<4>(s4, red);
+    S[kDXprev2] = s4[0]; S[kDX12] = s4[1]; S[kDYprev2] = s4[2]; S[kDY12] = s4[3];
+    const bool exact = c.set_approx(S, nrmA);
+    if (exact) {
+      // exact residuals (pogs.cpp:352-373)
+      row_dots<T, false>(A, n, m, full_row, x12, [&](int i, T s) { ytemp[i] = s - y12[i]; });
+      __syncthreads();
+      double r2[1] = {0};
+      for (int i = threadIdx.x; i < m; i += kTPB) r2[0] += static_cast<double>(ytemp[i]) * ytemp[i];
+      wg_sum<1>(r2, red);
+      for (int i = threadIdx.x; i < m; i += kTPB) ytemp[i] = (y12[i] + yt[i]) - yprev[i];
+      for (int j = threadIdx.x; j < n; j += kTPB) xtemp[j] = (x12[j] + xt[j]) - xprev[j];
+      __syncthreads();
+      col_dots<T, false>(A, n, m, n, all_cols, ytemp, [&](int j, T s) { xtemp[j] = xtemp[j] + s; }, part);
+      __syncthreads();
+      double s2[1] = {0};
+      for (int j = threadIdx.x; j < n; j += kTPB) s2[0] += static_cast<double>(xtemp[j]) * xtemp[j];
+      wg_sum<1>(s2, red);
+      S[kExactR2] = r2[0];
+      S[kExactS2] = s2[0];
+      c.set_exact(S);
+    }
+    const bool stop = c.check_stop(exact);
+    if (stop) {
+      // optval = f(y12) + g(x12) (pogs.cpp:473), then the un-scaled outputs (:510-518, 567-570)
+      double fv[2] = {0, 0};
+      for (int i = threadIdx.x; i < m; i += kTPB) {
+        const Coef<T> f = coef(F, i, d[i], true);
+        fv[0] += static_cast<double>(dev::FuncEval(f.h, f.a, f.b, f.c, f.d, f.e, y12[i]));
+      }
+      for (int j = threadIdx.x; j < n; j += kTPB) {
+        const Coef<T> g = coef(G, j, e[j], false);
+        fv[1] += static_cast<double>(dev::FuncEval(g.h, g.a, g.b, g.c, g.d, g.e, x12[j]));
+      }
+      wg_sum<2>(fv, red);
+      const T nr = -rho;
+      for (int i = threadIdx.x; i < m; i += kTPB) {
+        const size_t o = static_cast<size_t>(q) * m + i;
+        a.lo[o] = (((yt[i] - yprev[i]) + y12[i]) * nr) * d[i];
+        a.yo[o] = y12[i] / d[i];
+      }
+      for (int j = threadIdx.x; j < n; j += kTPB) {
+        const size_t o = static_cast<size_t>(q) * n + j;
+        a.muo[o] = (((xt[j] - xprev[j]) + x12[j]) * nr) / e[j];
+        a.xo[o] = x12[j] * e[j];
+      }
+      if (threadIdx.x == 0) {
+        a.optval[q] = static_cast<double>(static_cast<T>(fv[0]) + static_cast<T>(fv[1]));
+        a.iters[q] = c.k;
+        a.status[q] = c.status();
+        a.ctl[q] = c;
+        a.st[q].stopped = 1;
+        atomicAdd(a.done_count, 1u);
+      }
+      return;
+    }
+    const T scale = c.adapt();
+    ++c.k;
+    // zt += alpha z12 + (1 - alpha) zprev - z, then the rho change's rescaling (pogs.cpp:397-466)
+    for (int j = threadIdx.x; j < n; j += kTPB) xt[j] = (((xt[j] + alpha * x12[j]) + oma * xprev[j]) - x[j]) * scale;
+    for (int i = threadIdx.x; i < m; i += kTPB) yt[i] = (((yt[i] + alpha * y12[i]) + oma * yprev[i]) - y[i]) * scale;
+    rho = c.rho;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) a.ctl[q] = c;
+}
+
+// ---- host driver ------------------------------------------------------------------------------------
+
+size_t workspace_cap_bytes(int device) {
+  const char *env = std::getenv("POGS_AMD_MANY_WORKSPACE_MB");
+  if (env && env[0]) {
+    const double mb = std::atof(env);
+    if (mb > 0) return static_cast<size_t>(mb * (1 << 20));
+  }
+  size_t total = 0;
+  hipDeviceProp_t prop;
+  if (hipGetDeviceProperties(&prop, device) == hipSuccess) total = prop.totalGlobalMem;
+  return total ? total / 8 : (size_t(4) << 30);
+}
+
+template <typename T>
+void solve_many_t(int ord, int kk, size_t m_, size_t n_, const void *Ain, int mem, int device, const FnHost *f,
+                  const FnHost *g, const double *rho0, const SolveParams &p, const BatchOut &out) {
+  const double t0 = wall_s();
+  Ctx ctx;
+  ctx.init(device, 0);
+  hipStream_t s = ctx.stream;
+  const int m = static_cast<int>(m_), n = static_cast<int>(n_), K = std::min(m, n);
+  const bool tall = m > n;
+  const size_t mn = m_ * n_;
+  auto R64 = [](size_t v) { return round_up(v, 64); };
+  ManyArgs<T> a{};
+  a.m = m; a.n = n; a.k = K; a.tall = tall;
+  a.rowmaj = ord == ROW_MAJ;
+  size_t off = 0;
+  a.oA = off; off += R64(mn);
+  a.oW = off; off += R64(static_cast<size_t>(K) * K);
+  a.oT = off; off += R64(K);
+  for (int v = 0; v < kNumX; ++v) { a.ox[v] = off; off += R64(n_); }
+  for (int v = 0; v < kNumY; ++v) { a.oy[v] = off; off += R64(m_); }
+  a.stride = off;
+  // per problem: workspace, staged input, outputs, coefficient arrays, control
+  const size_t per = sizeof(T) * (off + (mem == POGS_AMD_HOST ? mn : 0) + 2 * (m_ + n_) + 5 * (m_ + n_)) +
+                     sizeof(int) * (m_ + n_) + sizeof(AdmmControl<T>) + sizeof(ManyState<T>) + 64;
+  const size_t cap = workspace_cap_bytes(ctx.device);
+  const int chunk = static_cast<int>(std::max<size_t>(1, std::min<size_t>(static_cast<size_t>(kk), cap / per)));
+
+  DevBuf<T> ws(static_cast<size_t>(chunk) * a.stride), stage, rnd(n_);
+  if (mem == POGS_AMD_HOST) stage.alloc(static_cast<size_t>(chunk) * mn);
+  DevBuf<T> xo(static_cast<size_t>(chunk) * n_), yo(static_cast<size_t>(chunk) * m_), lo(static_cast<size_t>(chunk) * m_),
+      muo(static_cast<size_t>(chunk) * n_);
+  DevBuf<double> optv(chunk);
+  DevBuf<unsigned> iters(chunk), done(1);
+  DevBuf<int> stat(chunk);
+  DevBuf<ManyFn<T>> fnd(2 * static_cast<size_t>(chunk));
+  DevBuf<AdmmControl<T>> ctld(chunk);
+  DevBuf<ManyState<T>> std_(chunk);
+  DevBuf<T> tpool(static_cast<size_t>(chunk) * 5 * (m_ + n_) + 1);
+  DevBuf<int> hpool(static_cast<size_t>(chunk) * (m_ + n_) + 1);
+  PinnedBuf<unsigned> hdone(1);
+  {
+    std::vector<T> r(n_);
+    rand_uniform_host(r.data(), n_);
+    POGS_HIP_CHECK(hipMemcpyAsync(rnd.p, r.data(), n_ * sizeof(T), hipMemcpyHostToDevice, s));
+    ctx.sync();
+  }
+  a.ws = ws.p; a.rnd = rnd.p; a.fn = fnd.p; a.ctl = ctld.p; a.st = std_.p; a.done_count = done.p;
+  a.xo = xo.p; a.yo = yo.p; a.lo = lo.p; a.muo = muo.p; a.optval = optv.p; a.iters = iters.p; a.status = stat.p;
+  // equil_helper.h:152-153, 159-160
+  a.ce = static_cast<T>(1e-4) * static_cast<T>(m_ + n_) / static_cast<T>(m_);
+  a.cd = static_cast<T>(1e-4) * static_cast<T>(m_ + n_) / static_cast<T>(n_);
+
+  const double pass_bytes = 2.0 * static_cast<double>(mn) * sizeof(T);
+  const int per_launch = static_cast<int>(std::max(1.0, std::min(50.0, kLaunchBytes / pass_bytes)));
+  const double iter_bytes = (2.0 * static_cast<double>(mn) + static_cast<double>(K) * K) * sizeof(T);
+  const int ipl = static_cast<int>(std::max(1.0, std::min<double>(kMaxIterPerLaunch, kLaunchBytes / iter_bytes)));
+  const int nb = (K + 63) / 64, ntiles = nb * (nb + 1) / 2;
+  const int copy_blocks = static_cast<int>(std::min<size_t>(64, (mn + kTPB - 1) / kTPB));
+
+  std::vector<T> tp;
+  std::vector<int> hp;
+  std::vector<ManyFn<T>> fh(2 * static_cast<size_t>(chunk));
+  std::vector<AdmmControl<T>> ch(chunk);
+  unsigned long long launches = 0;
+  double t_setup = 0, t_loop = 0;
+  int counts[7] = {0, 0, 0, 0, 0, 0, 0};
+  unsigned it_lo = ~0u, it_hi = 0;
+  for (int j0 = 0; j0 < kk; j0 += chunk) {
+    const int cnt = std::min(chunk, kk - j0);
+    const double tc0 = wall_s();
+    const T *src = static_cast<const T *>(Ain) + static_cast<size_t>(j0) * mn;
+    if (mem == POGS_AMD_HOST) {
+      POGS_HIP_CHECK(hipMemcpyAsync(stage.p, src, static_cast<size_t>(cnt) * mn * sizeof(T), hipMemcpyHostToDevice, s));
+      src = stage.p;
+    }
+    a.src = src;
+    // the functions: per-element fields packed into one upload, broadcast fields as values
+    tp.clear();
+    hp.clear();
+    for (int q = 0; q < cnt; ++q) {
+      for (int side = 0; side < 2; ++side) {
+        const FnHost &fn = side == 0 ? f[j0 + q] : g[j0 + q];
+        const size_t len = side == 0 ? m_ : n_;
+        warn_negative_coeffs<T>(fn, len);
+        ManyFn<T> &d = fh[2 * q + side];
+        const void *ptr[5] = {fn.a, fn.b, fn.c, fn.d, fn.e};
+        for (int fld = 0; fld < 5; ++fld) {
+          d.v[fld] = static_cast<T>(fn.s0[fld]);
+          d.p[fld] = nullptr;
+          if (ptr[fld]) {
+            d.p[fld] = tpool.p + tp.size();
+            const T *src_f = static_cast<const T *>(ptr[fld]);
+            tp.insert(tp.end(), src_f, src_f + len);
+          }
+        }
+        d.h0 = fn.h0;
+        d.h = nullptr;
+        if (fn.h) {
+          d.h = hpool.p + hp.size();
+          hp.insert(hp.end(), fn.h, fn.h + len);
+        }
+      }
+    }
+    if (!tp.empty()) POGS_HIP_CHECK(hipMemcpyAsync(tpool.p, tp.data(), tp.size() * sizeof(T), hipMemcpyHostToDevice, s));
+    if (!hp.empty()) POGS_HIP_CHECK(hipMemcpyAsync(hpool.p, hp.data(), hp.size() * sizeof(int), hipMemcpyHostToDevice, s));
+    POGS_HIP_CHECK(hipMemcpyAsync(fnd.p, fh.data(), 2 * static_cast<size_t>(cnt) * sizeof(ManyFn<T>),
+                                  hipMemcpyHostToDevice, s));
+    for (int q = 0; q < cnt; ++q) {
+      AdmmControl<T> &c = ch[q];
+      c = AdmmControl<T>();
+      c.abs_tol = static_cast<T>(p.abs_tol);
+      c.rel_tol = static_cast<T>(p.rel_tol);
+      c.max_iter = p.max_iter;
+      c.adaptive_rho = p.adaptive_rho;
+      c.gap_stop = p.gap_stop;
+      c.rho0 = static_cast<T>(rho0 ? rho0[j0 + q] : 1.0);
+      c.m_glob = m_;
+      c.n = n_;
+      c.reset();
+    }
+    POGS_HIP_CHECK(hipMemcpyAsync(ctld.p, ch.data(), static_cast<size_t>(cnt) * sizeof(AdmmControl<T>),
+                                  hipMemcpyHostToDevice, s));
+    POGS_HIP_CHECK(hipMemsetAsync(std_.p, 0, static_cast<size_t>(cnt) * sizeof(ManyState<T>), s));
+    POGS_HIP_CHECK(hipMemsetAsync(done.p, 0, sizeof(unsigned), s));
+    // zero work vectors: the cold start (z = zt = 0)
+    POGS_HIP_CHECK(hipMemsetAsync(ws.p, 0, static_cast<size_t>(cnt) * a.stride * sizeof(T), s));
+    // setup
+    hipLaunchKernelGGL(many_copy_kernel<T>, dim3(copy_blocks, cnt), dim3(kTPB), 0, s, a);
+    ++launches;
+    for (int p0 = 0; p0 < 50; p0 += per_launch) {
+      hipLaunchKernelGGL(many_sk_kernel<T>, dim3(cnt), dim3(kTPB), 0, s, a, p0, std::min(per_launch, 50 - p0));
+      ++launches;
+    }
+    hipLaunchKernelGGL(many_scale_kernel<T>, dim3(cnt), dim3(kTPB), 0, s, a);
+    ++launches;
+    for (int i0 = 0; i0 < 50; i0 += per_launch) {
+      hipLaunchKernelGGL(many_normest_kernel<T>, dim3(cnt), dim3(kTPB), 0, s, a, i0, std::min(per_launch, 50 - i0));
+      ++launches;
+    }
+    hipLaunchKernelGGL(many_gram_kernel<T>, dim3(ntiles, cnt), dim3(kTPB), 0, s, a);
+    hipLaunchKernelGGL(many_factor_kernel<T>, dim3(cnt), dim3(kTPB), 0, s, a);
+    launches += 2;
+    POGS_HIP_CHECK(hipGetLastError());
+    ctx.sync();
+    const double tc1 = wall_s();
+    t_setup += tc1 - tc0;
+    // the loop: every launch advances each live problem by at most ipl iterations
+    const unsigned long long max_launches = (p.max_iter + ipl - 1) / ipl + 1;
+    unsigned long long nl = 0;
+    for (;;) {
+      hipLaunchKernelGGL(many_loop_kernel<T>, dim3(cnt), dim3(kTPB), 0, s, a, ipl);
+      POGS_HIP_CHECK(hipGetLastError());
+      ++launches;
+      ++nl;
+      POGS_HIP_CHECK(hipMemcpyAsync(hdone.p, done.p, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+      POGS_HIP_CHECK(hipStreamSynchronize(s));
+      if (*hdone.p >= static_cast<unsigned>(cnt)) break;
+      POGS_CHECK(nl < max_launches, "many-problem solve: a problem did not stop within max_iter iterations");
+    }
+    t_loop += wall_s() - tc1;
+    // outputs of the chunk
+    auto d2h = [&](void *dst, const void *srcd, size_t bytes) {
+      POGS_HIP_CHECK(hipMemcpyAsync(dst, srcd, bytes, hipMemcpyDeviceToHost, s));
+    };
+    const size_t xb = static_cast<size_t>(cnt) * n_ * sizeof(T), yb = static_cast<size_t>(cnt) * m_ * sizeof(T);
+    d2h(static_cast<T *>(out.x) + static_cast<size_t>(j0) * n_, xo.p, xb);
+    if (out.y) d2h(static_cast<T *>(out.y) + static_cast<size_t>(j0) * m_, yo.p, yb);
+    if (out.l) d2h(static_cast<T *>(out.l) + static_cast<size_t>(j0) * m_, lo.p, yb);
+    if (out.mu) d2h(static_cast<T *>(out.mu) + static_cast<size_t>(j0) * n_, muo.p, xb);
+    if (out.optval) d2h(out.optval + j0, optv.p, cnt * sizeof(double));
+    d2h(out.final_iter + j0, iters.p, cnt * sizeof(unsigned));
+    d2h(out.status + j0, stat.p, cnt * sizeof(int));
+    POGS_HIP_CHECK(hipStreamSynchronize(s));
+    for (int q = 0; q < cnt; ++q) {
+      const int st = out.status[j0 + q];
+      ++counts[st >= 0 && st < 7 ? st : 6];
+      it_lo = std::min(it_lo, out.final_iter[j0 + q]);
+      it_hi = std::max(it_hi, out.final_iter[j0 + q]);
+    }
+  }
+  if (p.verbose > 0) {
+    std::printf("POGS-AMD many: %d problems of %d x %d (%s), %d per chunk; status", kk, m, n,
+                sizeof(T) == 8 ? "fp64" : "fp32", chunk);
+    for (int st = 0; st < 7; ++st)
+      if (counts[st]) std::printf(" %s: %d,", status_string(st), counts[st]);
+    std::printf(" iterations %u..%u; setup %.3e s, loop %.3e s, total %.3e s; %llu launches\n", it_lo, it_hi, t_setup,
+                t_loop, wall_s() - t0, launches);
+    std::fflush(stdout);
+  }
+}
+
+}  // namespace
+
+void solve_many(int dtype, int ord, int k, size_t m, size_t n, const void *A, int mem, int device, const FnHost *f,
+                const FnHost *g, const double *rho, const SolveParams &p, const BatchOut &out) {
+  POGS_CHECK(dtype == POGS_AMD_F32 || dtype == POGS_AMD_F64, "many-problem solve: unknown dtype");
+  POGS_CHECK(k >= 1, "many-problem solve: k must be >= 1");
+  POGS_CHECK(ord == ROW_MAJ || ord == COL_MAJ, "many-problem solve: unknown ord");
+  POGS_CHECK(mem == POGS_AMD_HOST || mem == POGS_AMD_DEVICE, "many-problem solve: unknown mem");
+  POGS_CHECK(A != nullptr, "many-problem solve: null A");
+  POGS_CHECK(m >= 1 && n >= 1, "many-problem solve: m and n must be >= 1");
+  POGS_CHECK(std::min(m, n) <= POGS_AMD_MANY_MIN_DIM_MAX, "many-problem solve: min(m, n) exceeds POGS_AMD_MANY_MIN_DIM_MAX");
+  POGS_CHECK(std::max(m, n) <= POGS_AMD_MANY_MAX_DIM_MAX, "many-problem solve: max(m, n) exceeds POGS_AMD_MANY_MAX_DIM_MAX");
+  POGS_CHECK(out.x && out.final_iter && out.status, "many-problem solve: x, final_iter and status must not be NULL");
+  if (dtype == POGS_AMD_F64) solve_many_t<double>(ord, k, m, n, A, mem, device, f, g, rho, p, out);
+  else solve_many_t<float>(ord, k, m, n, A, mem, device, f, g, rho, p, out);
+}
+
+}  // namespace pogs_amd

@@ -317,6 +317,123 @@ def solve_logistic_path(A, b, lambdas, abs_tol=1e-4, rel_tol=1e-4, max_iter=2500
     return _solve_path(A, b, lambdas, logistic_functions, abs_tol, rel_tol, max_iter, verbose, rho, dtype)
 
 
+def _fn_struct(f, count, dtype, keep):
+    """A function vector as a PogsAmdFn: per-element fields as typed host arrays (kept alive in `keep`), fields
+    that are still scalars as broadcast values (include/pogs_amd.h: PogsAmdSolveFn)."""
+    fv = _as_vector(f)
+    if len(fv) != count:
+        raise ValueError("function vector of length %d where %d is needed" % (len(fv), count))
+    st = _lib.PogsAmdFn()
+    for k in FunctionVector._FIELDS:
+        v = fv._v[k]
+        if isinstance(v, np.ndarray):
+            arr = np.ascontiguousarray(v, dtype=np.int32 if k == "h" else dtype)
+            keep.append(arr)
+            setattr(st, k, arr.ctypes.data)
+        else:
+            setattr(st, k, None)
+            setattr(st, k + "0", int(v) if k == "h" else float(v))
+    return st
+
+
+def _many_matrices(A, dtype):
+    """(k, m, n, pointer, mem, ord, dtype, device, keep-alive) of the k matrices of `solve_many`."""
+    if hasattr(A, "data_ptr") and hasattr(A, "is_cuda"):          # a torch tensor
+        import torch
+
+        if A.dim() != 3:
+            raise ValueError("solve_many: A must be a (k, m, n) tensor, got %d dimensions" % A.dim())
+        tdt = {torch.float32: np.float32, torch.float64: np.float64}.get(A.dtype)
+        if tdt is None:
+            raise ValueError("solve_many: A must be float32 or float64")
+        dt = _resolve_dtype(tdt if dtype is None else dtype)
+        if dt != np.dtype(tdt):
+            raise ValueError("solve_many: a device tensor is read in place: its dtype must be the solve's dtype")
+        k, m, n = A.shape
+        if not A.is_cuda:
+            return _many_matrices(A.numpy(), dt)
+        if A.is_contiguous():
+            order = Ordering.ROW_MAJ
+        elif A.stride() == (m * n, 1, m):
+            order = Ordering.COL_MAJ
+        else:
+            raise ValueError("solve_many: each matrix of a device tensor must be row- or column-major and packed")
+        _lib.check_device_pointer_interop()
+        return k, m, n, ctypes.c_void_p(A.data_ptr()), _lib.DEVICE, order, dt, A.device.index, A
+    if isinstance(A, (list, tuple)):
+        mats = [np.asarray(a) for a in A]
+        if not mats or any(a.ndim != 2 for a in mats) or any(a.shape != mats[0].shape for a in mats):
+            raise ValueError("solve_many: A as a list must hold k >= 1 two-dimensional arrays of one shape")
+        dt = _resolve_dtype(dtype)
+        arr = np.ascontiguousarray(np.stack([np.asarray(a, dtype=dt) for a in mats]))
+    else:
+        dt = _resolve_dtype(dtype)
+        arr = np.asarray(A)
+        if arr.ndim != 3:
+            raise ValueError("solve_many: A must be (k, m, n), got shape %s" % (arr.shape,))
+        arr = np.asarray(arr, dtype=dt)
+    k, m, n = arr.shape
+    isz = arr.itemsize
+    if arr.flags.c_contiguous:
+        order = Ordering.ROW_MAJ
+    elif arr.strides == (m * n * isz, isz, m * isz):      # every matrix Fortran-ordered, packed back to back
+        order = Ordering.COL_MAJ
+    else:
+        arr = np.ascontiguousarray(arr)
+        order = Ordering.ROW_MAJ
+    return k, m, n, _ptr(arr), _lib.HOST, order, dt, None, arr
+
+
+def solve_many(A, fs, gs, rho=1.0, abs_tol=1e-4, rel_tol=1e-4, max_iter=2500, verbose=0, adaptive_rho=True,
+               gap_stop=True, dtype=None, device=-1):
+    """Solve k independent graph-form problems, problem j with its own matrix A_j and functions (fs[j], gs[j]), in
+    one call on the GPU (include/pogs_amd.h: PogsAmdSolveManyFn).  Each is solved as the one-shot solve would solve
+    it; a problem's results do not depend on the other problems.
+
+    ``A``: a (k, m, n) ndarray (each matrix C- or Fortran-ordered), a list of k equal-shape 2-D arrays, or a
+    (k, m, n) torch tensor on a ROCm device (read in place, never written).  ``fs``, ``gs``: k function vectors /
+    lists of `FunctionObj`.  ``rho``: one value or k values.  ``device``: -1 = the tensor's device, else the
+    current one.  Returns {'x': k x n, 'y': k x m, 'l': k x m, 'mu': k x n, 'optval', 'iterations', 'status':
+    length k}.  verbose > 0 prints one summary for the call."""
+    k, m, n, aptr, mem, order, dt, tdev, keep_a = _many_matrices(A, dtype)
+    fs, gs = list(fs), list(gs)
+    if len(fs) != k or len(gs) != k:
+        raise ValueError("solve_many: %d matrices, %d f and %d g function vectors" % (k, len(fs), len(gs)))
+    if np.ndim(rho) == 0:
+        rhos = np.full(k, float(rho))
+    else:
+        rhos = np.ascontiguousarray(rho, dtype=np.float64).ravel()
+        if len(rhos) != k:
+            raise ValueError("solve_many: %d problems and %d rho values" % (k, len(rhos)))
+    keep = []
+    fa = (_lib.PogsAmdFn * k)()
+    ga = (_lib.PogsAmdFn * k)()
+    for j in range(k):
+        if len(fs[j]) != m or len(gs[j]) != n:
+            raise ValueError("solve_many: f must have length %d and g length %d, got %d and %d"
+                             % (m, n, len(fs[j]), len(gs[j])))
+        fa[j] = _fn_struct(fs[j], m, dt, keep)
+        ga[j] = _fn_struct(gs[j], n, dt, keep)
+    dev = tdev if (device == -1 and tdev is not None) else device
+    opt = _lib.PogsAmdOptions(device=dev, projector=_lib.PROJ_DIRECT)
+    x = np.zeros((k, n), dt)
+    y = np.zeros((k, m), dt)
+    l = np.zeros((k, m), dt)
+    mu = np.zeros((k, n), dt)
+    optval = np.zeros(k, np.float64)
+    final_iter = np.zeros(k, np.uint32)
+    status = np.zeros(k, np.int32)
+    code = _lib.F64 if dt == np.float64 else _lib.F32
+    st = lib.PogsAmdSolveManyFn(code, int(order), k, m, n, aptr, mem, ctypes.byref(opt), fa, ga, _ptr(rhos), abs_tol,
+                                rel_tol, int(max_iter), int(verbose), int(adaptive_rho), int(gap_stop), _ptr(x), _ptr(y),
+                                _ptr(l), _ptr(mu), _ptr(optval), _ptr(final_iter), _ptr(status))
+    del keep, keep_a
+    if st != 0:
+        raise RuntimeError("pogs_amd: many-problem solve failed: " + _lib.last_error())
+    return {"x": x, "y": y, "l": l, "mu": mu, "optval": optval, "iterations": final_iter.astype(np.int64),
+            "status": status.astype(np.int64)}
+
+
 def solve_ridge(A, b, lambd, abs_tol=1e-4, rel_tol=1e-4, max_iter=2500, verbose=0, rho=1.0, dtype=None):
     """minimize 0.5 ||A x - b||^2 + 0.5 lambda ||x||^2   (reference: graph.py:436-476)"""
     m, n = _shape(A)
