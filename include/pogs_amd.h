@@ -155,7 +155,10 @@ typedef struct PogsAmdStats {
                                           over A);
                                      [5] / [6] / [7]: with options.profile, the same batch's
                                           HIP-event time (ms), launch count and algorithmic bytes
-                                          of its multi-vector passes over A                       */
+                                          of its multi-vector passes over A;
+                                     after PogsAmdSolveBatchSparseFn the same, with `matvecs`
+                                          counting multi-vector products with A or A^T and
+                                          `cg_iters` batched CG steps                             */
 } PogsAmdStats;
 
 /* Fill `out` (POGS_AMD_UNIQUE_ID_BYTES) with a fresh RCCL unique id (rank 0
@@ -226,6 +229,22 @@ int PogsAmdSolveBatchFn(PogsAmdSolver *s, int k, const PogsAmdFn *f, const PogsA
                         double abs_tol, double rel_tol, unsigned int max_iter, unsigned int verbose,
                         int adaptive_rho, int gap_stop, void *x, void *y, void *l, void *mu,
                         double *optval, unsigned int *final_iter, int *status);
+
+/* Batched solves on a sparse handle: as PogsAmdSolveBatchFn (same arguments, output layout, shared parameters and
+ * per-problem rho), for a single-GPU sparse handle of any shape (m > n or m <= n), built from CSR or CSC, from host or
+ * device memory.  Every product with A or A^T reads the equilibrated matrix once for all active problems.  The
+ * projection is a batched CGLS: each problem runs its own CG (shift 1, at most 500 steps, its own tolerance,
+ * warm-started from its previous x) and leaves the product's slot list when its CG stops.  A problem's outputs do not
+ * depend on k, on its position or on the other problems.  Stats: `iterations` batch iterations, `matvecs`
+ * multi-vector products, `cg_iters` batched CG steps, reserved[4] problem-iterations, reserved[5..7] with
+ * options.profile the products' HIP-event time (ms), launch count and algorithmic bytes.
+ * Returns 0 when the batch ran (status[j] holds each PogsStatus), POGS_ERROR when refused (PogsAmdLastError says
+ * why): k out of range, a dense handle, row shards, or a NULL x, final_iter or status; the handle stays usable.  The
+ * handle's solo state (the last solo solve's stats but those above, its iterate, a pending warm start) is kept. */
+int PogsAmdSolveBatchSparseFn(PogsAmdSolver *s, int k, const PogsAmdFn *f, const PogsAmdFn *g, const double *rho,
+                              double abs_tol, double rel_tol, unsigned int max_iter, unsigned int verbose,
+                              int adaptive_rho, int gap_stop, void *x, void *y, void *l, void *mu,
+                              double *optval, unsigned int *final_iter, int *status);
 
 /* Many small problems, each with its own matrix: k independent graph-form problems, problem j with its own
  * m x n matrix A_j and its own f[j], g[j], rho[j].  Each one is solved exactly as the one-shot PogsD / PogsS call

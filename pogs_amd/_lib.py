@@ -125,6 +125,7 @@ lib.PogsAmdSolveFn.argtypes = [c_void_p, ctypes.POINTER(PogsAmdFn), ctypes.POINT
 lib.PogsAmdSolveBatchFn.argtypes = [c_void_p, c_int, ctypes.POINTER(PogsAmdFn), ctypes.POINTER(PogsAmdFn), c_void_p,
                                     c_double, c_double, c_uint, c_uint, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_void_p, c_void_p, c_void_p]
+lib.PogsAmdSolveBatchSparseFn.argtypes = lib.PogsAmdSolveBatchFn.argtypes
 BATCH_MAX = 16   # include/pogs_amd.h: POGS_AMD_BATCH_MAX
 lib.PogsAmdSolveManyFn.argtypes = [c_int, c_int, c_int, c_size_t, c_size_t, c_void_p, c_int, ctypes.POINTER(PogsAmdOptions),
                                    ctypes.POINTER(PogsAmdFn), ctypes.POINTER(PogsAmdFn), c_void_p, c_double, c_double,
@@ -181,7 +182,8 @@ def pool_trim(device=-1):
 # Every symbol include/pogs_amd.h declares (checked by tests/test_abi.py).
 ABI_SYMBOLS = [
     "PogsD", "PogsS", "PogsSparseD", "PogsSparseS",
-    "PogsAmdDistUniqueId", "PogsAmdCreateDense", "PogsAmdCreateSparse", "PogsAmdSolve", "PogsAmdSolveFn", "PogsAmdSolveBatchFn", "PogsAmdSolveManyFn", "PogsAmdBeginRun", "PogsAmdBeginRunFn",
+    "PogsAmdDistUniqueId", "PogsAmdCreateDense", "PogsAmdCreateSparse", "PogsAmdSolve", "PogsAmdSolveFn", "PogsAmdSolveBatchFn", "PogsAmdSolveBatchSparseFn",
+    "PogsAmdSolveManyFn", "PogsAmdBeginRun", "PogsAmdBeginRunFn",
     "PogsAmdIterate", "PogsAmdSetWarmStart", "PogsAmdGetStats", "PogsAmdResetStats", "PogsAmdDestroy", "PogsAmdLastError",
     "PogsAmdPoolStats", "PogsAmdPoolTrim",
     "PogsAmdProxEval", "PogsAmdFuncEval", "PogsAmdProjSubgradEval", "PogsAmdGetEquil", "PogsAmdProject", "PogsAmdMul", "PogsAmdRandUniform",

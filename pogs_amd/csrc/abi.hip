@@ -365,6 +365,28 @@ int PogsAmdSolveBatchFn(PogsAmdSolver *s, int k, const PogsAmdFn *f, const PogsA
   }, s);
 }
 
+int PogsAmdSolveBatchSparseFn(PogsAmdSolver *s, int k, const PogsAmdFn *f, const PogsAmdFn *g, const double *rho,
+                              double abs_tol, double rel_tol, unsigned int max_iter, unsigned int verbose,
+                              int adaptive_rho, int gap_stop, void *x, void *y, void *l, void *mu, double *optval,
+                              unsigned int *final_iter, int *status) {
+  return guarded([&]() {
+    POGS_CHECK(s && s->impl, "null solver");
+    POGS_CHECK(k >= 1 && k <= POGS_AMD_BATCH_MAX, "batched solve: k must be in [1, POGS_AMD_BATCH_MAX]");
+    POGS_CHECK(f && g, "batched solve: null function descriptions");
+    POGS_CHECK(x && final_iter && status, "batched solve: x, final_iter and status must not be NULL");
+    DeviceGuard guard(s->impl->device());
+    std::vector<FnHost> fh, gh;
+    for (int j = 0; j < k; ++j) {
+      fh.push_back(fn_host(&f[j]));
+      gh.push_back(fn_host(&g[j]));
+    }
+    s->impl->solve_batch_sparse(k, fh.data(), gh.data(), rho,
+                                make_params(1.0, abs_tol, rel_tol, max_iter, verbose, adaptive_rho, gap_stop),
+                                BatchOut{x, y, l, mu, optval, final_iter, status});
+    return 0;
+  }, s);
+}
+
 int PogsAmdSolveManyFn(int dtype, enum ORD ord, int k, size_t m, size_t n, const void *A, int mem,
                        const PogsAmdOptions *opt, const PogsAmdFn *f, const PogsAmdFn *g, const double *rho,
                        double abs_tol, double rel_tol, unsigned int max_iter, unsigned int verbose, int adaptive_rho,

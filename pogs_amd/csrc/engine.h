@@ -674,6 +674,11 @@ struct SolverBase {
   virtual void solve_batch(int, const FnHost *, const FnHost *, const double *, const SolveParams &, const BatchOut &) {
     throw Error("batched solves need a dense handle");
   }
+  // k problems on the handle's sparse matrix (one GPU); rho: k values or null
+  virtual void solve_batch_sparse(int, const FnHost *, const FnHost *, const double *, const SolveParams &,
+                                  const BatchOut &) {
+    throw Error("a batched sparse solve needs a sparse handle");
+  }
   virtual void iterate(unsigned iters, double *seconds, unsigned *solves) = 0;
   virtual void set_warm_start(const void *x0, const void *l0) = 0;
   virtual void get_equil(void *A_eq, void *d, void *e, double *nrmA) = 0;

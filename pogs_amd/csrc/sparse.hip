@@ -15,6 +15,7 @@
 // staged in LDS, rows reduced from there.  The solver itself runs on a tiled sliced-ELL copy of
 // each (sell.h): x slices and row sums in LDS, uint16 local columns, no partial-sum traffic.
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdio>
 #include <limits>
@@ -26,6 +27,7 @@
 #include "engine.h"
 #include "reduce.h"
 #include "sell.h"
+#include "sparse_batch_kernels.h"
 #include "vec_kernels.h"
 
 namespace pogs_amd {
@@ -623,6 +625,10 @@ class SparseSolver final : public SolverBase {
     apply_warm_start();
     ctx_.sync();
   }
+
+  // k problems on the handle's matrix, every product with A / A^T shared (sparse_batch.h)
+  void solve_batch_sparse(int kb, const FnHost *f, const FnHost *g, const double *rho0, const SolveParams &p,
+                          const BatchOut &out) override;
 
   void set_warm_start(const void *x0, const void *l0) override {
     warm_x_.assign(static_cast<const T *>(x0), static_cast<const T *>(x0) + n_);
@@ -1718,6 +1724,8 @@ class SparseSolver final : public SolverBase {
   T zt_scale_ = 1;
   T nrmA_ = 0;
 };
+
+#include "sparse_batch.h"
 
 }  // namespace
 

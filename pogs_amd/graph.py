@@ -609,7 +609,8 @@ class Solver:
     def solve_batch(self, fs, gs, rho=1.0, abs_tol=1e-4, rel_tol=1e-4, max_iter=2500, verbose=0, adaptive_rho=True,
                     gap_stop=True):
         """Solve len(fs) problems (f_j, g_j, rho_j) on this handle's matrix, every pass over A shared by up to
-        BATCH_MAX of them (include/pogs_amd.h: PogsAmdSolveBatchFn; dense, m > n, direct projector, one GPU).
+        BATCH_MAX of them (include/pogs_amd.h: PogsAmdSolveBatchFn on a dense handle -- m > n, direct projector,
+        one GPU; PogsAmdSolveBatchSparseFn on a sparse one -- any shape, one GPU).
         ``rho``: one value for all or a sequence.  Longer lists run as consecutive batches.  Returns a list of
         dicts with the keys `solve` returns.  The handle's solo state (a pending warm start included) is kept."""
         fs, gs = list(fs), list(gs)
@@ -626,6 +627,7 @@ class Solver:
             if len(f) != self.m or len(g) != self.n:
                 raise ValueError("solve_batch: f must have length %d and g length %d, got %d and %d"
                                  % (self.m, self.n, len(f), len(g)))
+        entry = lib.PogsAmdSolveBatchSparseFn if self.sparse else lib.PogsAmdSolveBatchFn
         out = []
         for lo in range(0, k, _lib.BATCH_MAX):
             hi = min(k, lo + _lib.BATCH_MAX)
@@ -645,9 +647,9 @@ class Solver:
             optval = np.zeros(kb, np.float64)
             final_iter = np.zeros(kb, np.uint32)
             status = np.zeros(kb, np.int32)
-            st = lib.PogsAmdSolveBatchFn(self._h, kb, fa, ga, _ptr(r), abs_tol, rel_tol, int(max_iter), int(verbose),
-                                         int(adaptive_rho), int(gap_stop), _ptr(x), _ptr(y), _ptr(l), _ptr(mu),
-                                         _ptr(optval), _ptr(final_iter), _ptr(status))
+            st = entry(self._h, kb, fa, ga, _ptr(r), abs_tol, rel_tol, int(max_iter), int(verbose), int(adaptive_rho),
+                       int(gap_stop), _ptr(x), _ptr(y), _ptr(l), _ptr(mu), _ptr(optval), _ptr(final_iter),
+                       _ptr(status))
             del keep
             if st != 0:
                 raise RuntimeError("pogs_amd: batched solve failed: " + _lib.last_error())
