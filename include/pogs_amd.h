@@ -357,12 +357,48 @@ int PogsAmdMul(PogsAmdSolver *s, char trans, double alpha, const void *x, double
  * row-block shape of the dense pass), `reps` timed launches each.  bench.py prints it as
  * roofline.peak_measured next to the data-sheet peak.  *pattern (may be NULL): 0 or 1, which one won. */
 int PogsAmdReadBandwidth(int device, size_t bytes, int reps, double *gb_per_s, int *pattern);
-/* Diagnostic: the 64-lane wavefront sums behind every row dot-product and scalar of the engine are formed in the
- * vector ALU (v_permlane32_swap / v_permlane16_swap / DPP, csrc/reduce.h) in the order of the butterfly
- * `v += shfl_xor(v, 32, 16, 8, 4, 2, 1)`.  For n (a multiple of 64) HOST values this returns, per value, its
- * wavefront's total formed that way (alu) and by the butterfly through the LDS crossbar (lds): the two must agree
- * bit for bit (tests/test_gpu_dense.py). */
+/* Diagnostic: the 64-lane wavefront sums of the engine formed in the vector ALU (dev::wave_sum_valu:
+ * v_permlane32_swap / v_permlane16_swap / DPP, csrc/reduce.h) in the order of the butterfly
+ * `v += shfl_xor(v, 32, 16, 8, 4, 2, 1)` -- the fp32 tree of the streaming row dots and the fp64 tree of every
+ * scalar sum.  For n (a multiple of 64) HOST values this returns, per value, its wavefront's total formed that way
+ * (alu) and by the butterfly through the LDS crossbar (lds): the two must agree bit for bit
+ * (tests/test_gpu_dense.py). */
 int PogsAmdWaveSumCheck(int dtype, size_t n, const void *in_host, void *alu_host, void *lds_host);
+
+/* Diagnostics of the batched and many-problem kernels.  Every array is a HOST pointer of type dtype (0 fp32,
+ * 1 fp64) unless noted; each entry uploads its inputs, runs the launch functions and geometry the solvers call, and
+ * downloads the results.  k (1 <= k <= POGS_AMD_BATCH_MAX) problems are stored at stride ld in X / Y / U / Z;
+ * act[0 .. nact) (1 <= nact <= k, distinct, in [0, k)) lists the problems of the launch, slot q running problem
+ * act[q].  Output arrays are uploaded before the launch and downloaded after it, so entries a launch does not write
+ * come back as they were.  VEC = 16 / sizeof(element) (4 fp32, 2 fp64), cols_pad = round_up(cols, VEC).  Invalid
+ * arguments are refused before any device work: POGS_ERROR, and PogsAmdLastError says why. */
+/* Y[p][r] = sum_c M[r][c] X[p][c] for r < rows and the problems p of act (the batched solve's launch_batch_rows).
+ * M: rows x ldm row-major; ldm, ldx: multiples of VEC, >= cols_pad; ldy >= rows.  tri: 0 full, 1 lower (c <= r),
+ * 2 upper (c >= r) triangle of a square M (rows == cols); entries outside the triangle and M's columns >= cols are
+ * never used.  Contract of the caller (dense_batch.h keeps it): X[p][c] == 0 for cols <= c < cols_pad. */
+int PogsAmdBatchRowsCheck(int dtype, int tri, int rows, int cols, const void *M, size_t ldm, int k, const int *act,
+                          int nact, const void *X, size_t ldx, void *Y, size_t ldy);
+/* Z[p][c] = sum_r M[r][c] U[p][r] (+ add[p][c] when add is not NULL) for c < cols, Z[p][c] = 0 for
+ * cols <= c < cols_pad (launch_batch_cols over the row-block partition of the batched solve, then
+ * launch_batch_cols_reduce).  M: rows x ldm row-major, ldm a multiple of VEC, >= cols_pad; ldu >= rows;
+ * ldz >= cols_pad (also add's).  *nrb_used and *rpb report the partition: row blocks and rows per block. */
+int PogsAmdBatchColsCheck(int dtype, int rows, int cols, const void *M, size_t ldm, int k, const int *act, int nact,
+                          const void *U, size_t ldu, const void *add, void *Z, size_t ldz, int *nrb_used, int *rpb);
+/* Y[p][r] = sum_q val[q] X[p][ind[q]] over ptr[r] <= q < ptr[r+1] (+ beta yin[p][r] when yin is not NULL), the
+ * batched sparse solve's product (sp_batch_geometry, launch_sp_batch_pack, launch_sp_batch_spmv).  CSR of
+ * nrows x ncols: ptr (nrows + 1, ptr[0] == 0, non-decreasing), ind in [0, ncols) (int32).  ldx >= ncols,
+ * ldy >= nrows, ldin >= nrows.  part (doubles, may be NULL): part[p * grid + w] = the sum of the squares of the Y
+ * values of workgroup w; it must hold k * max(1, ceil(nrows / 4)) doubles (>= k * grid).  num_cu: the CU count the
+ * geometry is chosen for (0: the device's).  geom (3 ints) = {log2 lanes per row, rows per workgroup, grid}. */
+int PogsAmdSpBatchSpmvCheck(int dtype, int nrows, int ncols, const int *ptr, const int *ind, const void *val, int k,
+                            const int *act, int nact, const void *X, size_t ldx, double beta, const void *yin,
+                            size_t ldin, void *Y, size_t ldy, double *part, int num_cu, int *geom);
+/* The setup of PogsAmdSolveManyFn on k problems in one chunk (its launch sequence: copy, Sinkhorn-Knopp, scale,
+ * norm estimate, Gram tiles, Cholesky, W = L^-1); arguments and refusals as there.  Per problem j (HOST outputs,
+ * any may be NULL): A_eq + j m n (m x n row-major), d + j m, e + j n, nrmA[j], and W + j K^2 with K = min(m, n):
+ * K x K row-major, W = L^-1 in its lower triangle for L L^T = I + A_eq^T A_eq (m > n) or I + A_eq A_eq^T. */
+int PogsAmdManySetupCheck(int dtype, enum ORD ord, int k, size_t m, size_t n, const void *A, int mem, void *A_eq,
+                          void *d, void *e, double *nrmA, void *W);
 /* The Norm2Est start vector (reference: gsl::rand, src/cpu/include/gsl/gsl_rand.h:8-16). */
 int PogsAmdRandUniform(int dtype, size_t n, void *out_host);
 

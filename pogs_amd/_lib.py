@@ -152,6 +152,16 @@ lib.PogsAmdMul.argtypes = [c_void_p, c_char, c_double, c_void_p, c_double, c_voi
 lib.PogsAmdRandUniform.argtypes = [c_int, c_size_t, c_void_p]
 lib.PogsAmdReadBandwidth.argtypes = [c_int, c_size_t, c_int, ctypes.POINTER(c_double), ctypes.POINTER(c_int)]
 lib.PogsAmdWaveSumCheck.argtypes = [c_int, c_size_t, c_void_p, c_void_p, c_void_p]
+lib.PogsAmdBatchRowsCheck.argtypes = [c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_int, c_void_p, c_int,
+                                      c_void_p, c_size_t, c_void_p, c_size_t]
+lib.PogsAmdBatchColsCheck.argtypes = [c_int, c_int, c_int, c_void_p, c_size_t, c_int, c_void_p, c_int, c_void_p,
+                                      c_size_t, c_void_p, c_void_p, c_size_t, ctypes.POINTER(c_int),
+                                      ctypes.POINTER(c_int)]
+lib.PogsAmdSpBatchSpmvCheck.argtypes = [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
+                                        c_void_p, c_size_t, c_double, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p,
+                                        c_int, c_void_p]
+lib.PogsAmdManySetupCheck.argtypes = [c_int, c_int, c_int, c_size_t, c_size_t, c_void_p, c_int, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p]
 
 
 class PogsAmdPoolInfo(ctypes.Structure):
@@ -187,7 +197,8 @@ ABI_SYMBOLS = [
     "PogsAmdIterate", "PogsAmdSetWarmStart", "PogsAmdGetStats", "PogsAmdResetStats", "PogsAmdDestroy", "PogsAmdLastError",
     "PogsAmdPoolStats", "PogsAmdPoolTrim",
     "PogsAmdProxEval", "PogsAmdFuncEval", "PogsAmdProjSubgradEval", "PogsAmdGetEquil", "PogsAmdProject", "PogsAmdMul", "PogsAmdRandUniform",
-    "PogsAmdReadBandwidth", "PogsAmdWaveSumCheck",
+    "PogsAmdReadBandwidth", "PogsAmdWaveSumCheck", "PogsAmdBatchRowsCheck", "PogsAmdBatchColsCheck",
+    "PogsAmdSpBatchSpmvCheck", "PogsAmdManySetupCheck",
 ]
 
 
@@ -209,6 +220,112 @@ def wave_sum_check(values):
     if lib.PogsAmdWaveSumCheck(0 if v.dtype == np.float32 else 1, v.size, v.ctypes.data, a.ctypes.data, b.ctypes.data) != 0:
         raise RuntimeError(last_error())
     return a, b
+
+
+def _dtype_code(*arrays):
+    import numpy as np
+    dt = arrays[0].dtype
+    if dt not in (np.float32, np.float64) or any(a.dtype != dt for a in arrays[1:]):
+        raise ValueError("float32 or float64 arrays of one dtype")
+    return 0 if dt == np.float32 else 1
+
+
+def _act(act):
+    import numpy as np
+    return np.ascontiguousarray(act, dtype=np.int32).ravel()
+
+
+def batch_rows_check(tri, M, cols, X, Y, act):
+    """Y with Y[p, r] = sum_c M[r, c] X[p, c] for the problems p of act, by the batched solve's row-dot kernel
+    (include/pogs_amd.h: PogsAmdBatchRowsCheck).  M: rows x ldm, X: k x ldx, Y: k x ldy (C-contiguous, one float
+    dtype); tri 0 / 1 / 2: full / lower / upper triangle.  Returns a new array; Y itself is not changed."""
+    import numpy as np
+    M, X = np.ascontiguousarray(M), np.ascontiguousarray(X)
+    Y = np.array(Y, order="C", copy=True)
+    code = _dtype_code(M, X, Y)
+    if M.ndim != 2 or X.ndim != 2 or Y.ndim != 2 or X.shape[0] != Y.shape[0]:
+        raise ValueError("M (rows, ldm), X (k, ldx), Y (k, ldy)")
+    a = _act(act)
+    if lib.PogsAmdBatchRowsCheck(code, tri, M.shape[0], cols, M.ctypes.data, M.shape[1], X.shape[0], a.ctypes.data,
+                                 a.size, X.ctypes.data, X.shape[1], Y.ctypes.data, Y.shape[1]) != 0:
+        raise RuntimeError(last_error())
+    return Y
+
+
+def batch_cols_check(M, cols, U, Z, act, add=None):
+    """(Z, nrb_used, rpb): Z[p, c] = sum_r M[r, c] U[p, r] (+ add[p, c]) for the problems p of act by the batched
+    solve's column-sum kernels (include/pogs_amd.h: PogsAmdBatchColsCheck), and the row-block partition they used.
+    M: rows x ldm, U: k x ldu, Z and add: k x ldz.  Returns a new array; Z itself is not changed."""
+    import numpy as np
+    M, U = np.ascontiguousarray(M), np.ascontiguousarray(U)
+    Z = np.array(Z, order="C", copy=True)
+    arrays = (M, U, Z) if add is None else (M, U, Z, np.ascontiguousarray(add))
+    code = _dtype_code(*arrays)
+    if M.ndim != 2 or U.ndim != 2 or Z.ndim != 2 or U.shape[0] != Z.shape[0] or \
+            (add is not None and arrays[3].shape != Z.shape):
+        raise ValueError("M (rows, ldm), U (k, ldu), Z and add (k, ldz)")
+    a = _act(act)
+    nrb, rpb = c_int(0), c_int(0)
+    if lib.PogsAmdBatchColsCheck(code, M.shape[0], cols, M.ctypes.data, M.shape[1], U.shape[0], a.ctypes.data, a.size,
+                                 U.ctypes.data, U.shape[1], None if add is None else arrays[3].ctypes.data,
+                                 Z.ctypes.data, Z.shape[1], ctypes.byref(nrb), ctypes.byref(rpb)) != 0:
+        raise RuntimeError(last_error())
+    return Z, nrb.value, rpb.value
+
+
+def sp_batch_spmv_check(ptr, ind, val, ncols, X, Y, act, beta=0.0, yin=None, part_fill=None, num_cu=0):
+    """(Y, part, (lshift, rpw, grid)): Y[p, r] = (CSR x X[p])[r] (+ beta yin[p, r]) for the problems p of act by
+    the batched sparse solve's product (include/pogs_amd.h: PogsAmdSpBatchSpmvCheck).  X: k x ldx, Y and yin:
+    k x ldy / k x ldin.  part_fill: None (no records) or the value the k x grid record array starts as.  Returns a
+    new array; Y itself is not changed."""
+    import numpy as np
+    ptr, ind = np.ascontiguousarray(ptr, dtype=np.int32), np.ascontiguousarray(ind, dtype=np.int32)
+    val, X = np.ascontiguousarray(val), np.ascontiguousarray(X)
+    Y = np.array(Y, order="C", copy=True)
+    arrays = (val, X, Y) if yin is None else (val, X, Y, np.ascontiguousarray(yin))
+    code = _dtype_code(*arrays)
+    nrows = ptr.size - 1
+    if X.ndim != 2 or Y.ndim != 2 or X.shape[0] != Y.shape[0] or nrows < 0 or \
+            (yin is not None and (arrays[3].ndim != 2 or arrays[3].shape[0] != Y.shape[0])):
+        raise ValueError("ptr (nrows + 1), X (k, ldx), Y (k, ldy), yin (k, ldin)")
+    nnz = max(int(ptr[-1]), 0) if ptr.size else 0
+    if ind.size < nnz or val.size < nnz:
+        raise ValueError("ind and val must hold ptr[-1] entries")
+    a = _act(act)
+    k = X.shape[0]
+    part = None
+    if part_fill is not None:
+        part = np.full(k * max(1, -(-nrows // 4)), part_fill, dtype=np.float64)
+    geom = np.zeros(3, dtype=np.int32)
+    if lib.PogsAmdSpBatchSpmvCheck(code, nrows, ncols, ptr.ctypes.data, ind.ctypes.data, val.ctypes.data, k,
+                                   a.ctypes.data, a.size, X.ctypes.data, X.shape[1], beta,
+                                   None if yin is None else arrays[3].ctypes.data,
+                                   0 if yin is None else arrays[3].shape[1], Y.ctypes.data, Y.shape[1],
+                                   None if part is None else part.ctypes.data, num_cu, geom.ctypes.data) != 0:
+        raise RuntimeError(last_error())
+    grid = int(geom[2])
+    return Y, (None if part is None else part[:k * grid].reshape(k, grid)), tuple(int(g) for g in geom)
+
+
+def many_setup_check(A, ord=ROW_MAJ):
+    """The setup of a many-problem solve (include/pogs_amd.h: PogsAmdManySetupCheck) on A (k x m x n): dict of
+    A_eq (k, m, n), d (k, m), e (k, n), nrmA (k,) and W (k, K, K), K = min(m, n), W = L^-1 in the lower triangle.
+    ord = COL_MAJ hands the library each matrix stored column-major."""
+    import numpy as np
+    A = np.asarray(A)
+    if A.ndim != 3:
+        raise ValueError("A must be k x m x n")
+    code = _dtype_code(A)
+    k, m, n = A.shape
+    src = np.ascontiguousarray(A.transpose(0, 2, 1) if ord == COL_MAJ else A)
+    K = min(m, n)
+    out = dict(A_eq=np.empty((k, m, n), A.dtype), d=np.empty((k, m), A.dtype), e=np.empty((k, n), A.dtype),
+               nrmA=np.empty(k, np.float64), W=np.empty((k, K, K), A.dtype))
+    if lib.PogsAmdManySetupCheck(code, ord, k, m, n, src.ctypes.data, HOST, out["A_eq"].ctypes.data,
+                                 out["d"].ctypes.data, out["e"].ctypes.data, out["nrmA"].ctypes.data,
+                                 out["W"].ctypes.data) != 0:
+        raise RuntimeError(last_error())
+    return out
 
 
 def last_error():

@@ -6,6 +6,7 @@
 
 #include "engine.h"
 #include "many_kernels.h"
+#include "sparse_batch_kernels.h"
 #include "prox.h"
 #include "stream.h"
 #include "vec_kernels.h"
@@ -580,6 +581,62 @@ int PogsAmdWaveSumCheck(int dtype, size_t n, const void *in_host, void *alu_host
     POGS_CHECK(in_host && alu_host && lds_host, "null argument");
     if (dtype == POGS_AMD_F32) wave_sum_check(static_cast<const float *>(in_host), n, static_cast<float *>(alu_host), static_cast<float *>(lds_host));
     else wave_sum_check(static_cast<const double *>(in_host), n, static_cast<double *>(alu_host), static_cast<double *>(lds_host));
+    return 0;
+  });
+}
+
+int PogsAmdBatchRowsCheck(int dtype, int tri, int rows, int cols, const void *M, size_t ldm, int k, const int *act,
+                          int nact, const void *X, size_t ldx, void *Y, size_t ldy) {
+  return guarded([&]() {
+    POGS_CHECK(dtype == POGS_AMD_F32 || dtype == POGS_AMD_F64, "unknown dtype");
+    if (dtype == POGS_AMD_F32)
+      batch_rows_check<float>(tri, rows, cols, static_cast<const float *>(M), ldm, k, act, nact,
+                              static_cast<const float *>(X), ldx, static_cast<float *>(Y), ldy);
+    else
+      batch_rows_check<double>(tri, rows, cols, static_cast<const double *>(M), ldm, k, act, nact,
+                               static_cast<const double *>(X), ldx, static_cast<double *>(Y), ldy);
+    return 0;
+  });
+}
+
+int PogsAmdBatchColsCheck(int dtype, int rows, int cols, const void *M, size_t ldm, int k, const int *act, int nact,
+                          const void *U, size_t ldu, const void *add, void *Z, size_t ldz, int *nrb_used, int *rpb) {
+  return guarded([&]() {
+    POGS_CHECK(dtype == POGS_AMD_F32 || dtype == POGS_AMD_F64, "unknown dtype");
+    if (dtype == POGS_AMD_F32)
+      batch_cols_check<float>(rows, cols, static_cast<const float *>(M), ldm, k, act, nact,
+                              static_cast<const float *>(U), ldu, static_cast<const float *>(add),
+                              static_cast<float *>(Z), ldz, nrb_used, rpb);
+    else
+      batch_cols_check<double>(rows, cols, static_cast<const double *>(M), ldm, k, act, nact,
+                               static_cast<const double *>(U), ldu, static_cast<const double *>(add),
+                               static_cast<double *>(Z), ldz, nrb_used, rpb);
+    return 0;
+  });
+}
+
+int PogsAmdSpBatchSpmvCheck(int dtype, int nrows, int ncols, const int *ptr, const int *ind, const void *val, int k,
+                            const int *act, int nact, const void *X, size_t ldx, double beta, const void *yin,
+                            size_t ldin, void *Y, size_t ldy, double *part, int num_cu, int *geom) {
+  return guarded([&]() {
+    POGS_CHECK(dtype == POGS_AMD_F32 || dtype == POGS_AMD_F64, "unknown dtype");
+    if (dtype == POGS_AMD_F32)
+      sp_batch_spmv_check<float>(nrows, ncols, ptr, ind, static_cast<const float *>(val), k, act, nact,
+                                 static_cast<const float *>(X), ldx, static_cast<float>(beta),
+                                 static_cast<const float *>(yin), ldin, static_cast<float *>(Y), ldy, part, num_cu,
+                                 geom);
+    else
+      sp_batch_spmv_check<double>(nrows, ncols, ptr, ind, static_cast<const double *>(val), k, act, nact,
+                                  static_cast<const double *>(X), ldx, beta, static_cast<const double *>(yin), ldin,
+                                  static_cast<double *>(Y), ldy, part, num_cu, geom);
+    return 0;
+  });
+}
+
+int PogsAmdManySetupCheck(int dtype, enum ORD ord, int k, size_t m, size_t n, const void *A, int mem, void *A_eq,
+                          void *d, void *e, double *nrmA, void *W) {
+  return guarded([&]() {
+    many_setup_check(dtype, static_cast<int>(ord), k, m, n, A, mem, A_eq, d, e, nrmA, W);
     return 0;
   });
 }

@@ -61,6 +61,16 @@ void launch_batch_cols(const T *M, size_t ldm, int rows, int cols_pad, int rows_
 // columns per slab of launch_batch_cols
 template <typename T>
 constexpr int batch_cols_slab() { return 64 / static_cast<int>(sizeof(T)) * 4; }
+// Row-block partition of launch_batch_cols over a rows x cols_pad matrix: from the shape only (the same for every k
+// and slot).  rpb: rows per block, a multiple of 16; nrb_used: the blocks that hold rows.
+template <typename T>
+inline void batch_cols_partition(int rows, int cols_pad, int &rpb, int &nrb_used) {
+  constexpr int SLAB = batch_cols_slab<T>();
+  const int ncs = (cols_pad + SLAB - 1) / SLAB;
+  const int nrb = std::max(1, std::min((rows + 63) / 64, (4096 + ncs - 1) / ncs));
+  rpb = static_cast<int>(round_up(static_cast<size_t>((rows + nrb - 1) / nrb), 16));
+  nrb_used = (rows + rpb - 1) / rpb;
+}
 // Z[p][c] = sum_rb part[rb][p][c] in row-block order (+ add[p][c]); columns >= cols are zero
 template <typename T>
 void launch_batch_cols_reduce(const T *part, int nrb, int kb, int cols, int cols_pad, const T *add, T *Z, size_t ldz,
@@ -71,5 +81,31 @@ template <typename T> void launch_batch_tail(const BatchVecArgs<T> &a, hipStream
 template <typename T> void launch_batch_exact_u(const BatchVecArgs<T> &a, hipStream_t s);
 template <typename T> void launch_batch_exact(const BatchVecArgs<T> &a, hipStream_t s);
 void launch_batch_sums(const BatchSumJobs &jobs, int njobs, const BatchSlots &sl, double *out, hipStream_t s);
+
+// The slots of the diagnostic entries (PogsAmdBatchRowsCheck, ...): k problems, nact of them active, act without
+// repeats and inside [0, k).  Throws Error otherwise.
+inline BatchSlots checked_batch_slots(int k, const int *act, int nact) {
+  POGS_CHECK(k >= 1 && k <= kBatchMax, "k must be in [1, POGS_AMD_BATCH_MAX]");
+  POGS_CHECK(nact >= 1 && nact <= k, "nact must be in [1, k]");
+  POGS_CHECK(act != nullptr, "null act");
+  BatchSlots sl;
+  bool seen[kBatchMax] = {};
+  for (int q = 0; q < nact; ++q) {
+    POGS_CHECK(act[q] >= 0 && act[q] < k, "act entry out of range [0, k)");
+    POGS_CHECK(!seen[act[q]], "act entry repeats");
+    seen[act[q]] = true;
+    sl.act[q] = act[q];
+  }
+  sl.nact = nact;
+  return sl;
+}
+// Diagnostics behind PogsAmdBatchRowsCheck / PogsAmdBatchColsCheck (HOST arrays; include/pogs_amd.h): argument checks,
+// upload, the solver's launches, download.
+template <typename T>
+void batch_rows_check(int tri, int rows, int cols, const T *M, size_t ldm, int k, const int *act, int nact, const T *X,
+                      size_t ldx, T *Y, size_t ldy);
+template <typename T>
+void batch_cols_check(int rows, int cols, const T *M, size_t ldm, int k, const int *act, int nact, const T *U,
+                      size_t ldu, const T *add, T *Z, size_t ldz, int *nrb_used, int *rpb);
 
 }  // namespace pogs_amd

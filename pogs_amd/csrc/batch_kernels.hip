@@ -345,6 +345,59 @@ void launch_batch_sums(const BatchSumJobs &jobs, int njobs, const BatchSlots &sl
   hipLaunchKernelGGL(batch_sum_kernel, dim3(njobs, sl.nact), dim3(256), 0, s, jobs, sl, out);
 }
 
+template <typename T>
+void batch_rows_check(int tri, int rows, int cols, const T *M, size_t ldm, int k, const int *act, int nact, const T *X,
+                      size_t ldx, T *Y, size_t ldy) {
+  constexpr size_t VEC = Vec16<T>::N;
+  const BatchSlots sl = checked_batch_slots(k, act, nact);
+  POGS_CHECK(tri == kFull || tri == kLower || tri == kUpper, "unknown tri (0 full, 1 lower, 2 upper)");
+  POGS_CHECK(rows >= 1 && cols >= 1, "rows and cols must be >= 1");
+  POGS_CHECK(tri == kFull || rows == cols, "a triangle needs rows == cols");
+  POGS_CHECK(M && X && Y, "null argument");
+  const size_t cols_pad = round_up(static_cast<size_t>(cols), VEC);
+  POGS_CHECK(ldm >= cols_pad && ldm % VEC == 0, "ldm must be a multiple of VEC and >= round_up(cols, VEC)");
+  POGS_CHECK(ldx >= cols_pad && ldx % VEC == 0, "ldx must be a multiple of VEC and >= round_up(cols, VEC)");
+  POGS_CHECK(ldy >= static_cast<size_t>(rows), "ldy must be >= rows");
+  const size_t nm = static_cast<size_t>(rows) * ldm, nx = static_cast<size_t>(k) * ldx, ny = static_cast<size_t>(k) * ldy;
+  DevBuf<T> dM(nm), dX(nx), dY(ny);
+  POGS_HIP_CHECK(hipMemcpy(dM.p, M, nm * sizeof(T), hipMemcpyHostToDevice));
+  POGS_HIP_CHECK(hipMemcpy(dX.p, X, nx * sizeof(T), hipMemcpyHostToDevice));
+  POGS_HIP_CHECK(hipMemcpy(dY.p, Y, ny * sizeof(T), hipMemcpyHostToDevice));
+  launch_batch_rows<T>(tri, dM.p, ldm, rows, cols, static_cast<int>(cols_pad), dX.p, ldx, dY.p, ldy, sl, nullptr);
+  POGS_HIP_CHECK(hipGetLastError());
+  POGS_HIP_CHECK(hipMemcpy(Y, dY.p, ny * sizeof(T), hipMemcpyDeviceToHost));
+  POGS_HIP_CHECK(hipDeviceSynchronize());
+}
+
+template <typename T>
+void batch_cols_check(int rows, int cols, const T *M, size_t ldm, int k, const int *act, int nact, const T *U,
+                      size_t ldu, const T *add, T *Z, size_t ldz, int *nrb_used, int *rpb) {
+  constexpr size_t VEC = Vec16<T>::N;
+  const BatchSlots sl = checked_batch_slots(k, act, nact);
+  POGS_CHECK(rows >= 1 && cols >= 1, "rows and cols must be >= 1");
+  POGS_CHECK(M && U && Z && nrb_used && rpb, "null argument");
+  const size_t cols_pad = round_up(static_cast<size_t>(cols), VEC);
+  POGS_CHECK(ldm >= cols_pad && ldm % VEC == 0, "ldm must be a multiple of VEC and >= round_up(cols, VEC)");
+  POGS_CHECK(ldu >= static_cast<size_t>(rows), "ldu must be >= rows");
+  POGS_CHECK(ldz >= cols_pad, "ldz must be >= round_up(cols, VEC)");
+  int rb = 0, nrb = 0;
+  batch_cols_partition<T>(rows, static_cast<int>(cols_pad), rb, nrb);
+  const size_t nm = static_cast<size_t>(rows) * ldm, nu = static_cast<size_t>(k) * ldu, nz = static_cast<size_t>(k) * ldz;
+  DevBuf<T> dM(nm), dU(nu), dZ(nz), dA(add ? nz : 0), part(static_cast<size_t>(nrb) * k * cols_pad);
+  POGS_HIP_CHECK(hipMemcpy(dM.p, M, nm * sizeof(T), hipMemcpyHostToDevice));
+  POGS_HIP_CHECK(hipMemcpy(dU.p, U, nu * sizeof(T), hipMemcpyHostToDevice));
+  POGS_HIP_CHECK(hipMemcpy(dZ.p, Z, nz * sizeof(T), hipMemcpyHostToDevice));
+  if (add) POGS_HIP_CHECK(hipMemcpy(dA.p, add, nz * sizeof(T), hipMemcpyHostToDevice));
+  launch_batch_cols<T>(dM.p, ldm, rows, static_cast<int>(cols_pad), rb, nrb, dU.p, ldu, part.p, k, sl, nullptr);
+  launch_batch_cols_reduce<T>(part.p, nrb, k, cols, static_cast<int>(cols_pad), add ? dA.p : nullptr, dZ.p, ldz, sl,
+                              nullptr);
+  POGS_HIP_CHECK(hipGetLastError());
+  POGS_HIP_CHECK(hipMemcpy(Z, dZ.p, nz * sizeof(T), hipMemcpyDeviceToHost));
+  POGS_HIP_CHECK(hipDeviceSynchronize());
+  *nrb_used = nrb;
+  *rpb = rb;
+}
+
 #define POGS_BATCH_INST(T)                                                                                             \
   template void launch_batch_rows<T>(int, const T *, size_t, int, int, int, const T *, size_t, T *, size_t,             \
                                      const BatchSlots &, hipStream_t);                                                   \
@@ -355,7 +408,11 @@ void launch_batch_sums(const BatchSumJobs &jobs, int njobs, const BatchSlots &sl
   template void launch_batch_pre<T>(const BatchVecArgs<T> &, hipStream_t);                                             \
   template void launch_batch_tail<T>(const BatchVecArgs<T> &, hipStream_t);                                            \
   template void launch_batch_exact_u<T>(const BatchVecArgs<T> &, hipStream_t);                                         \
-  template void launch_batch_exact<T>(const BatchVecArgs<T> &, hipStream_t);
+  template void launch_batch_exact<T>(const BatchVecArgs<T> &, hipStream_t);                                          \
+  template void batch_rows_check<T>(int, int, int, const T *, size_t, int, const int *, int, const T *, size_t, T *,  \
+                                    size_t);                                                                           \
+  template void batch_cols_check<T>(int, int, const T *, size_t, int, const int *, int, const T *, size_t, const T *, \
+                                    T *, size_t, int *, int *);
 POGS_BATCH_INST(float)
 POGS_BATCH_INST(double)
 

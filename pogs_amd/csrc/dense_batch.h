@@ -49,11 +49,8 @@ void DenseSolver<T, Tag>::solve_batch(int kb, const FnHost *f, const FnHost *g, 
   DevBuf<FnView<T>> dviews(2 * kb);
   POGS_HIP_CHECK(hipMemcpyAsync(dviews.p, views.data(), views.size() * sizeof(FnView<T>), hipMemcpyHostToDevice, s));
   // column-sum partials: row blocks chosen from the shape only (the same for every k and slot)
-  constexpr int SLAB = batch_cols_slab<T>();
-  const int ncs = (n_pad_ + SLAB - 1) / SLAB;
-  const int nrb = std::max(1, std::min((m + 63) / 64, (4096 + ncs - 1) / ncs));
-  const int rpb = static_cast<int>(round_up(static_cast<size_t>((m + nrb - 1) / nrb), 16));
-  const int nrb_used = (m + rpb - 1) / rpb;
+  int rpb = 0, nrb_used = 0;
+  batch_cols_partition<T>(m, n_pad_, rpb, nrb_used);
   DevBuf<T> bpart(static_cast<size_t>(nrb_used) * kb * n_pad_);
   const int vbx = vec_blocks(n), vby = vec_blocks(m);
   DevBuf<double> vpart(static_cast<size_t>(kb) * (vbx + vby) * 3), tpart(static_cast<size_t>(kb) * (vbx + vby) * 2),

@@ -12,4 +12,9 @@ namespace pogs_amd {
 void solve_many(int dtype, int ord, int k, size_t m, size_t n, const void *A, int mem, int device, const FnHost *f,
                 const FnHost *g, const double *rho, const SolveParams &p, const BatchOut &out);
 
+// PogsAmdManySetupCheck (include/pogs_amd.h): the setup of a solve on k problems in one chunk, HOST outputs (any may
+// be null).  Refusals as solve_many's, before any device work.
+void many_setup_check(int dtype, int ord, int k, size_t m, size_t n, const void *A, int mem, void *A_eq, void *d,
+                      void *e, double *nrmA, void *W);
+
 }  // namespace pogs_amd

@@ -549,6 +549,108 @@ size_t workspace_cap_bytes(int device) {
   return total ? total / 8 : (size_t(4) << 30);
 }
 
+// The shape fields of ManyArgs: the problem's workspace layout (offsets in elements of T) and the Sinkhorn-Knopp
+// regularisers (equil_helper.h:152-153, 159-160).
+template <typename T>
+void many_layout(ManyArgs<T> &a, int ord, size_t m_, size_t n_) {
+  const int m = static_cast<int>(m_), n = static_cast<int>(n_), K = std::min(m, n);
+  auto R64 = [](size_t v) { return round_up(v, 64); };
+  a.m = m; a.n = n; a.k = K; a.tall = m > n;
+  a.rowmaj = ord == ROW_MAJ;
+  size_t off = 0;
+  a.oA = off; off += R64(m_ * n_);
+  a.oW = off; off += R64(static_cast<size_t>(K) * K);
+  a.oT = off; off += R64(K);
+  for (int v = 0; v < kNumX; ++v) { a.ox[v] = off; off += R64(n_); }
+  for (int v = 0; v < kNumY; ++v) { a.oy[v] = off; off += R64(m_); }
+  a.stride = off;
+  a.ce = static_cast<T>(1e-4) * static_cast<T>(m_ + n_) / static_cast<T>(m_);
+  a.cd = static_cast<T>(1e-4) * static_cast<T>(m_ + n_) / static_cast<T>(n_);
+}
+
+// The Norm2Est start vector (n values) into rnd.
+template <typename T>
+void many_start_vector(T *rnd, size_t n, hipStream_t s) {
+  std::vector<T> r(n);
+  rand_uniform_host(r.data(), n);
+  POGS_HIP_CHECK(hipMemcpyAsync(rnd, r.data(), n * sizeof(T), hipMemcpyHostToDevice, s));
+  POGS_HIP_CHECK(hipStreamSynchronize(s));
+}
+
+// The setup of the cnt problems of a chunk (a: many_layout's fields, ws, st, src and rnd set): zero workspaces and
+// states, then copy, all 50 Sinkhorn-Knopp passes, scale, norm estimate, Gram tiles, factor and W = L^-1.  Returns the
+// number of launches.  The solve and PogsAmdManySetupCheck both run this sequence.
+template <typename T>
+unsigned long long many_setup(const ManyArgs<T> &a, int cnt, hipStream_t s) {
+  const size_t mn = static_cast<size_t>(a.m) * a.n;
+  const int K = a.k;
+  const double pass_bytes = 2.0 * static_cast<double>(mn) * sizeof(T);
+  const int per_launch = static_cast<int>(std::max(1.0, std::min(50.0, kLaunchBytes / pass_bytes)));
+  const int nb = (K + 63) / 64, ntiles = nb * (nb + 1) / 2;
+  const int copy_blocks = static_cast<int>(std::min<size_t>(64, (mn + kTPB - 1) / kTPB));
+  unsigned long long launches = 0;
+  POGS_HIP_CHECK(hipMemsetAsync(a.st, 0, static_cast<size_t>(cnt) * sizeof(ManyState<T>), s));
+  // zero work vectors: the cold start (z = zt = 0)
+  POGS_HIP_CHECK(hipMemsetAsync(a.ws, 0, static_cast<size_t>(cnt) * a.stride * sizeof(T), s));
+  hipLaunchKernelGGL(many_copy_kernel<T>, dim3(copy_blocks, cnt), dim3(kTPB), 0, s, a);
+  ++launches;
+  for (int p0 = 0; p0 < 50; p0 += per_launch) {
+    hipLaunchKernelGGL(many_sk_kernel<T>, dim3(cnt), dim3(kTPB), 0, s, a, p0, std::min(per_launch, 50 - p0));
+    ++launches;
+  }
+  hipLaunchKernelGGL(many_scale_kernel<T>, dim3(cnt), dim3(kTPB), 0, s, a);
+  ++launches;
+  for (int i0 = 0; i0 < 50; i0 += per_launch) {
+    hipLaunchKernelGGL(many_normest_kernel<T>, dim3(cnt), dim3(kTPB), 0, s, a, i0, std::min(per_launch, 50 - i0));
+    ++launches;
+  }
+  hipLaunchKernelGGL(many_gram_kernel<T>, dim3(ntiles, cnt), dim3(kTPB), 0, s, a);
+  hipLaunchKernelGGL(many_factor_kernel<T>, dim3(cnt), dim3(kTPB), 0, s, a);
+  launches += 2;
+  POGS_HIP_CHECK(hipGetLastError());
+  return launches;
+}
+
+// PogsAmdManySetupCheck: many_setup on k problems in one chunk, then per problem A_eq, d, e, nrmA and W (K x K).
+template <typename T>
+void many_setup_check_t(int ord, int kk, size_t m_, size_t n_, const void *Ain, int mem, T *A_eq, T *d, T *e,
+                        double *nrmA, T *W) {
+  Ctx ctx;
+  ctx.init(-1, 0);
+  hipStream_t s = ctx.stream;
+  const size_t mn = m_ * n_;
+  ManyArgs<T> a{};
+  many_layout(a, ord, m_, n_);
+  const size_t K = static_cast<size_t>(a.k);
+  DevBuf<T> ws(static_cast<size_t>(kk) * a.stride), stage, rnd(n_);
+  DevBuf<ManyState<T>> st(kk);
+  many_start_vector(rnd.p, n_, s);
+  const T *src = static_cast<const T *>(Ain);
+  if (mem == POGS_AMD_HOST) {
+    stage.alloc(static_cast<size_t>(kk) * mn);
+    POGS_HIP_CHECK(hipMemcpyAsync(stage.p, src, static_cast<size_t>(kk) * mn * sizeof(T), hipMemcpyHostToDevice, s));
+    src = stage.p;
+  }
+  a.ws = ws.p; a.rnd = rnd.p; a.st = st.p; a.src = src;
+  many_setup(a, kk, s);
+  std::vector<ManyState<T>> hst(kk);
+  POGS_HIP_CHECK(hipMemcpyAsync(hst.data(), st.p, static_cast<size_t>(kk) * sizeof(ManyState<T>), hipMemcpyDeviceToHost,
+                                s));
+  for (int q = 0; q < kk; ++q) {
+    const T *w = ws.p + static_cast<size_t>(q) * a.stride;
+    auto d2h = [&](T *dst, size_t off, size_t len) {
+      if (dst) POGS_HIP_CHECK(hipMemcpyAsync(dst + q * len, w + off, len * sizeof(T), hipMemcpyDeviceToHost, s));
+    };
+    d2h(A_eq, a.oA, mn);
+    d2h(d, a.oy[kD], m_);
+    d2h(e, a.ox[kE], n_);
+    d2h(W, a.oW, K * K);
+  }
+  POGS_HIP_CHECK(hipStreamSynchronize(s));
+  if (nrmA)
+    for (int q = 0; q < kk; ++q) nrmA[q] = static_cast<double>(hst[q].nrmA);
+}
+
 template <typename T>
 void solve_many_t(int ord, int kk, size_t m_, size_t n_, const void *Ain, int mem, int device, const FnHost *f,
                   const FnHost *g, const double *rho0, const SolveParams &p, const BatchOut &out) {
@@ -557,21 +659,11 @@ void solve_many_t(int ord, int kk, size_t m_, size_t n_, const void *Ain, int me
   ctx.init(device, 0);
   hipStream_t s = ctx.stream;
   const int m = static_cast<int>(m_), n = static_cast<int>(n_), K = std::min(m, n);
-  const bool tall = m > n;
   const size_t mn = m_ * n_;
-  auto R64 = [](size_t v) { return round_up(v, 64); };
   ManyArgs<T> a{};
-  a.m = m; a.n = n; a.k = K; a.tall = tall;
-  a.rowmaj = ord == ROW_MAJ;
-  size_t off = 0;
-  a.oA = off; off += R64(mn);
-  a.oW = off; off += R64(static_cast<size_t>(K) * K);
-  a.oT = off; off += R64(K);
-  for (int v = 0; v < kNumX; ++v) { a.ox[v] = off; off += R64(n_); }
-  for (int v = 0; v < kNumY; ++v) { a.oy[v] = off; off += R64(m_); }
-  a.stride = off;
+  many_layout(a, ord, m_, n_);
   // per problem: workspace, staged input, outputs, coefficient arrays, control
-  const size_t per = sizeof(T) * (off + (mem == POGS_AMD_HOST ? mn : 0) + 2 * (m_ + n_) + 5 * (m_ + n_)) +
+  const size_t per = sizeof(T) * (a.stride + (mem == POGS_AMD_HOST ? mn : 0) + 2 * (m_ + n_) + 5 * (m_ + n_)) +
                      sizeof(int) * (m_ + n_) + sizeof(AdmmControl<T>) + sizeof(ManyState<T>) + 64;
   const size_t cap = workspace_cap_bytes(ctx.device);
   const int chunk = static_cast<int>(std::max<size_t>(1, std::min<size_t>(static_cast<size_t>(kk), cap / per)));
@@ -589,24 +681,12 @@ void solve_many_t(int ord, int kk, size_t m_, size_t n_, const void *Ain, int me
   DevBuf<T> tpool(static_cast<size_t>(chunk) * 5 * (m_ + n_) + 1);
   DevBuf<int> hpool(static_cast<size_t>(chunk) * (m_ + n_) + 1);
   PinnedBuf<unsigned> hdone(1);
-  {
-    std::vector<T> r(n_);
-    rand_uniform_host(r.data(), n_);
-    POGS_HIP_CHECK(hipMemcpyAsync(rnd.p, r.data(), n_ * sizeof(T), hipMemcpyHostToDevice, s));
-    ctx.sync();
-  }
+  many_start_vector(rnd.p, n_, s);
   a.ws = ws.p; a.rnd = rnd.p; a.fn = fnd.p; a.ctl = ctld.p; a.st = std_.p; a.done_count = done.p;
   a.xo = xo.p; a.yo = yo.p; a.lo = lo.p; a.muo = muo.p; a.optval = optv.p; a.iters = iters.p; a.status = stat.p;
-  // equil_helper.h:152-153, 159-160
-  a.ce = static_cast<T>(1e-4) * static_cast<T>(m_ + n_) / static_cast<T>(m_);
-  a.cd = static_cast<T>(1e-4) * static_cast<T>(m_ + n_) / static_cast<T>(n_);
 
-  const double pass_bytes = 2.0 * static_cast<double>(mn) * sizeof(T);
-  const int per_launch = static_cast<int>(std::max(1.0, std::min(50.0, kLaunchBytes / pass_bytes)));
   const double iter_bytes = (2.0 * static_cast<double>(mn) + static_cast<double>(K) * K) * sizeof(T);
   const int ipl = static_cast<int>(std::max(1.0, std::min<double>(kMaxIterPerLaunch, kLaunchBytes / iter_bytes)));
-  const int nb = (K + 63) / 64, ntiles = nb * (nb + 1) / 2;
-  const int copy_blocks = static_cast<int>(std::min<size_t>(64, (mn + kTPB - 1) / kTPB));
 
   std::vector<T> tp;
   std::vector<int> hp;
@@ -671,27 +751,8 @@ void solve_many_t(int ord, int kk, size_t m_, size_t n_, const void *Ain, int me
     }
     POGS_HIP_CHECK(hipMemcpyAsync(ctld.p, ch.data(), static_cast<size_t>(cnt) * sizeof(AdmmControl<T>),
                                   hipMemcpyHostToDevice, s));
-    POGS_HIP_CHECK(hipMemsetAsync(std_.p, 0, static_cast<size_t>(cnt) * sizeof(ManyState<T>), s));
     POGS_HIP_CHECK(hipMemsetAsync(done.p, 0, sizeof(unsigned), s));
-    // zero work vectors: the cold start (z = zt = 0)
-    POGS_HIP_CHECK(hipMemsetAsync(ws.p, 0, static_cast<size_t>(cnt) * a.stride * sizeof(T), s));
-    // setup
-    hipLaunchKernelGGL(many_copy_kernel<T>, dim3(copy_blocks, cnt), dim3(kTPB), 0, s, a);
-    ++launches;
-    for (int p0 = 0; p0 < 50; p0 += per_launch) {
-      hipLaunchKernelGGL(many_sk_kernel<T>, dim3(cnt), dim3(kTPB), 0, s, a, p0, std::min(per_launch, 50 - p0));
-      ++launches;
-    }
-    hipLaunchKernelGGL(many_scale_kernel<T>, dim3(cnt), dim3(kTPB), 0, s, a);
-    ++launches;
-    for (int i0 = 0; i0 < 50; i0 += per_launch) {
-      hipLaunchKernelGGL(many_normest_kernel<T>, dim3(cnt), dim3(kTPB), 0, s, a, i0, std::min(per_launch, 50 - i0));
-      ++launches;
-    }
-    hipLaunchKernelGGL(many_gram_kernel<T>, dim3(ntiles, cnt), dim3(kTPB), 0, s, a);
-    hipLaunchKernelGGL(many_factor_kernel<T>, dim3(cnt), dim3(kTPB), 0, s, a);
-    launches += 2;
-    POGS_HIP_CHECK(hipGetLastError());
+    launches += many_setup(a, cnt, s);
     ctx.sync();
     const double tc1 = wall_s();
     t_setup += tc1 - tc0;
@@ -755,6 +816,24 @@ void solve_many(int dtype, int ord, int k, size_t m, size_t n, const void *A, in
   POGS_CHECK(out.x && out.final_iter && out.status, "many-problem solve: x, final_iter and status must not be NULL");
   if (dtype == POGS_AMD_F64) solve_many_t<double>(ord, k, m, n, A, mem, device, f, g, rho, p, out);
   else solve_many_t<float>(ord, k, m, n, A, mem, device, f, g, rho, p, out);
+}
+
+void many_setup_check(int dtype, int ord, int k, size_t m, size_t n, const void *A, int mem, void *A_eq, void *d,
+                      void *e, double *nrmA, void *W) {
+  POGS_CHECK(dtype == POGS_AMD_F32 || dtype == POGS_AMD_F64, "many setup check: unknown dtype");
+  POGS_CHECK(k >= 1, "many setup check: k must be >= 1");
+  POGS_CHECK(ord == ROW_MAJ || ord == COL_MAJ, "many setup check: unknown ord");
+  POGS_CHECK(mem == POGS_AMD_HOST || mem == POGS_AMD_DEVICE, "many setup check: unknown mem");
+  POGS_CHECK(A != nullptr, "many setup check: null A");
+  POGS_CHECK(m >= 1 && n >= 1, "many setup check: m and n must be >= 1");
+  POGS_CHECK(std::min(m, n) <= POGS_AMD_MANY_MIN_DIM_MAX, "many setup check: min(m, n) exceeds POGS_AMD_MANY_MIN_DIM_MAX");
+  POGS_CHECK(std::max(m, n) <= POGS_AMD_MANY_MAX_DIM_MAX, "many setup check: max(m, n) exceeds POGS_AMD_MANY_MAX_DIM_MAX");
+  if (dtype == POGS_AMD_F64)
+    many_setup_check_t<double>(ord, k, m, n, A, mem, static_cast<double *>(A_eq), static_cast<double *>(d),
+                               static_cast<double *>(e), nrmA, static_cast<double *>(W));
+  else
+    many_setup_check_t<float>(ord, k, m, n, A, mem, static_cast<float *>(A_eq), static_cast<float *>(d),
+                              static_cast<float *>(e), nrmA, static_cast<float *>(W));
 }
 
 }  // namespace pogs_amd

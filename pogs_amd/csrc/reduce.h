@@ -82,8 +82,10 @@ __device__ __forceinline__ double wave_sum(double v) {
   halves(v, lo, hi); v += whole(dpp_u32<0xB1>(lo), dpp_u32<0xB1>(hi));
   return v;
 }
-// (the same tree through the LDS crossbar: what the two above are tested against, tests/test_gpu_kernels)
+// (for doubles the tree in the vector ALU is wave_sum itself)
 __device__ __forceinline__ double wave_sum_valu(double v) { return wave_sum(v); }
+// (the same tree through the LDS crossbar: what wave_sum_valu(float) and wave_sum(double) are tested against --
+//  PogsAmdWaveSumCheck, tests/test_gpu_dense.py: test_wavefront_sum_in_the_alu_is_the_butterfly_bit_for_bit)
 template <typename T>
 __device__ __forceinline__ T wave_sum_shfl(T v) {
 #pragma unroll

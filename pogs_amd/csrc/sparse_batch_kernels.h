@@ -41,6 +41,14 @@ template <typename T>
 void launch_sp_batch_spmv(const SpBatchCsr<T> &M, const T *Xp, const BatchSlots &sl, T *Y, size_t ldy, const T *yin,
                           size_t ldin, T beta, double *part, hipStream_t s);
 
+// Diagnostic behind PogsAmdSpBatchSpmvCheck (HOST arrays; include/pogs_amd.h): argument checks, upload,
+// sp_batch_geometry (num_cu = 0: the device's CU count), launch_sp_batch_pack, launch_sp_batch_spmv, download.
+// geom = {lshift, rpw, grid}; part (may be null) receives k * grid doubles.
+template <typename T>
+void sp_batch_spmv_check(int nrows, int ncols, const int *ptr, const int *ind, const T *val, int k, const int *act,
+                         int nact, const T *X, size_t ldx, T beta, const T *yin, size_t ldin, T *Y, size_t ldy,
+                         double *part, int num_cu, int *geom);
+
 // batched CGLS (cgls.h:200-323), one problem per grid row (slot).  cg: [kb][kSbCg] device scalars, sums: the
 // problem's records of kBatchRec doubles (launch_batch_sums) at the slots of SpBatchSum
 enum SpBatchSum : int { kSbQ2 = 0, kSbX2 = 1, kSbS2 = 2, kSbP2 = 3 };

@@ -330,6 +330,58 @@ void launch_sp_batch_cg_scalars(int mode, const BatchSlots &sl, const double *su
   hipLaunchKernelGGL(sp_batch_cg_scalars_kernel, dim3(1), dim3(64), 0, s, mode, sl, sums, cg, shift, eps);
 }
 
+template <typename T>
+void sp_batch_spmv_check(int nrows, int ncols, const int *ptr, const int *ind, const T *val, int k, const int *act,
+                         int nact, const T *X, size_t ldx, T beta, const T *yin, size_t ldin, T *Y, size_t ldy,
+                         double *part, int num_cu, int *geom) {
+  const BatchSlots sl = checked_batch_slots(k, act, nact);
+  POGS_CHECK(nrows >= 1 && ncols >= 1, "nrows and ncols must be >= 1");
+  POGS_CHECK(ptr && X && Y && geom, "null argument");
+  POGS_CHECK(ptr[0] == 0, "ptr[0] must be 0");
+  for (int r = 0; r < nrows; ++r) POGS_CHECK(ptr[r + 1] >= ptr[r], "CSR row pointers must not decrease");
+  const size_t nnz = static_cast<size_t>(ptr[nrows]);
+  POGS_CHECK(nnz == 0 || (ind && val), "null ind / val");
+  for (size_t q = 0; q < nnz; ++q) POGS_CHECK(ind[q] >= 0 && ind[q] < ncols, "column index out of range [0, ncols)");
+  POGS_CHECK(ldx >= static_cast<size_t>(ncols), "ldx must be >= ncols");
+  POGS_CHECK(ldy >= static_cast<size_t>(nrows), "ldy must be >= nrows");
+  POGS_CHECK(!yin || ldin >= static_cast<size_t>(nrows), "ldin must be >= nrows");
+  POGS_CHECK(num_cu >= 0, "num_cu must be >= 0 (0: the device's)");
+  int cu = num_cu;
+  if (cu == 0) {
+    int dev = 0;
+    hipDeviceProp_t prop;
+    POGS_HIP_CHECK(hipGetDevice(&dev));
+    POGS_HIP_CHECK(hipGetDeviceProperties(&prop, dev));
+    cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;   // (Ctx::init's)
+  }
+  const size_t nx = static_cast<size_t>(k) * ldx, ny = static_cast<size_t>(k) * ldy;
+  const size_t nin = yin ? static_cast<size_t>(k) * ldin : 0;
+  DevBuf<int> dptr(static_cast<size_t>(nrows) + 1), dind(std::max<size_t>(nnz, 1));
+  DevBuf<T> dval(std::max<size_t>(nnz, 1)), dX(nx), dY(ny), dyin(nin),
+      pk(static_cast<size_t>(ncols) * sp_batch_kp(sl.nact));
+  POGS_HIP_CHECK(hipMemcpy(dptr.p, ptr, (static_cast<size_t>(nrows) + 1) * sizeof(int), hipMemcpyHostToDevice));
+  if (nnz) {
+    POGS_HIP_CHECK(hipMemcpy(dind.p, ind, nnz * sizeof(int), hipMemcpyHostToDevice));
+    POGS_HIP_CHECK(hipMemcpy(dval.p, val, nnz * sizeof(T), hipMemcpyHostToDevice));
+  }
+  POGS_HIP_CHECK(hipMemcpy(dX.p, X, nx * sizeof(T), hipMemcpyHostToDevice));
+  POGS_HIP_CHECK(hipMemcpy(dY.p, Y, ny * sizeof(T), hipMemcpyHostToDevice));
+  if (yin) POGS_HIP_CHECK(hipMemcpy(dyin.p, yin, nin * sizeof(T), hipMemcpyHostToDevice));
+  const SpBatchCsr<T> M = sp_batch_geometry(dval.p, dind.p, dptr.p, nrows, nnz, cu);
+  const size_t npart = static_cast<size_t>(k) * M.grid;
+  DevBuf<double> dpart(part ? npart : 0);
+  if (part) POGS_HIP_CHECK(hipMemcpy(dpart.p, part, npart * sizeof(double), hipMemcpyHostToDevice));
+  launch_sp_batch_pack<T>(dX.p, ldx, ncols, sl, pk.p, nullptr);
+  launch_sp_batch_spmv<T>(M, pk.p, sl, dY.p, ldy, yin ? dyin.p : nullptr, ldin, beta, part ? dpart.p : nullptr, nullptr);
+  POGS_HIP_CHECK(hipGetLastError());
+  POGS_HIP_CHECK(hipMemcpy(Y, dY.p, ny * sizeof(T), hipMemcpyDeviceToHost));
+  if (part) POGS_HIP_CHECK(hipMemcpy(part, dpart.p, npart * sizeof(double), hipMemcpyDeviceToHost));
+  POGS_HIP_CHECK(hipDeviceSynchronize());
+  geom[0] = M.lshift;
+  geom[1] = M.rpw;
+  geom[2] = M.grid;
+}
+
 #define POGS_SP_BATCH_INST(T)                                                                                          \
   template void launch_sp_batch_pack<T>(const T *, size_t, int, const BatchSlots &, T *, hipStream_t);                 \
   template void launch_sp_batch_spmv<T>(const SpBatchCsr<T> &, const T *, const BatchSlots &, T *, size_t, const T *,  \
@@ -337,7 +389,9 @@ void launch_sp_batch_cg_scalars(int mode, const BatchSlots &sl, const double *su
   template void launch_sp_batch_cg_init<T>(const SpBatchCgArgs<T> &, hipStream_t);                                     \
   template void launch_sp_batch_cg_xr<T>(const SpBatchCgArgs<T> &, hipStream_t);                                       \
   template void launch_sp_batch_cg_p<T>(const SpBatchCgArgs<T> &, hipStream_t);                                        \
-  template void launch_sp_batch_cg_close<T>(const SpBatchCgArgs<T> &, hipStream_t);
+  template void launch_sp_batch_cg_close<T>(const SpBatchCgArgs<T> &, hipStream_t);                                   \
+  template void sp_batch_spmv_check<T>(int, int, const int *, const int *, const T *, int, const int *, int,           \
+                                       const T *, size_t, T, const T *, size_t, T *, size_t, double *, int, int *);
 POGS_SP_BATCH_INST(float)
 POGS_SP_BATCH_INST(double)
 

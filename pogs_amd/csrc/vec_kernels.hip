@@ -545,15 +545,16 @@ double measure_read_bandwidth_gbs(size_t bytes, int reps, int *pattern) {
   return best;
 }
 
-// Diagnostic (PogsAmdWaveSumCheck): dev::wave_sum -- the wavefront total formed in the vector ALU -- next to the same
-// butterfly through __shfl_xor, per wavefront of 64 consecutive inputs; every lane's total is written.
+// Diagnostic (PogsAmdWaveSumCheck): dev::wave_sum_valu -- the wavefront total formed in the vector ALU (for fp64 that
+// is dev::wave_sum) -- next to the same butterfly through __shfl_xor, per wavefront of 64 consecutive inputs; every
+// lane's total is written.
 namespace {
 template <typename T>
 __global__ void __launch_bounds__(256) wave_sum_check_kernel(const T *in, size_t n, T *out_alu, T *out_lds) {
   const size_t i = static_cast<size_t>(blockIdx.x) * 256 + threadIdx.x;
   if (i >= n) return;   // (n is a multiple of 64: whole wavefronts leave together)
   const T v = in[i];
-  out_alu[i] = dev::wave_sum(v);
+  out_alu[i] = dev::wave_sum_valu(v);
   out_lds[i] = dev::wave_sum_shfl(v);
 }
 }  // namespace

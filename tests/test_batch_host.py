@@ -72,3 +72,63 @@ def test_length_mismatches_raise_before_the_library(monkeypatch):
     f2, g2 = graph.lasso_functions(b, 0.1, 11)
     with pytest.raises(ValueError):
         s.solve_batch([f, f2], [g, g2])                         # g length
+
+
+def _valid_call_runs_or_lacks_a_device(call):
+    """After refusals the entry still works: on a GPU box the valid call runs; without one it gets as far as the
+    device and fails there, not at an argument check."""
+    try:
+        return call()
+    except RuntimeError as e:
+        assert "HIP error" in str(e), str(e)
+        return None
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_batch_rows_check_refusals(dtype):
+    V = 16 // np.dtype(dtype).itemsize
+    M, X, Y = np.zeros((8, 8), dtype), np.zeros((3, 8), dtype), np.zeros((3, 8), dtype)
+    bad = {
+        "k must be in": lambda: _lib.batch_rows_check(0, M, 8, np.zeros((17, 8), dtype), np.zeros((17, 8), dtype), [0]),
+        "nact must be in": lambda: _lib.batch_rows_check(0, M, 8, X, Y, [0, 1, 2, 0]),
+        "act entry repeats": lambda: _lib.batch_rows_check(0, M, 8, X, Y, [1, 1]),
+        "act entry out of range": lambda: _lib.batch_rows_check(0, M, 8, X, Y, [3]),
+        "ldm must be": lambda: _lib.batch_rows_check(0, M, 8 + 1, X, Y, [0]),
+        "ldx must be": lambda: _lib.batch_rows_check(0, M, 8, X[:, :8 - V], Y, [0]),
+        "ldy must be": lambda: _lib.batch_rows_check(0, M, 8, X, Y[:, :7], [0]),
+        "unknown tri": lambda: _lib.batch_rows_check(3, M, 8, X, Y, [0]),
+        "triangle needs rows == cols": lambda: _lib.batch_rows_check(1, M[:5], 8, X, Y, [0]),
+    }
+    for msg, call in bad.items():
+        with pytest.raises(RuntimeError, match=msg):
+            call()
+        assert msg in _lib.last_error()
+    M[:] = 1
+    X[:] = 2
+    out = _valid_call_runs_or_lacks_a_device(lambda: _lib.batch_rows_check(0, M, 8, X, Y, [2, 0]))
+    if out is not None:
+        assert np.all(out[[0, 2]] == 16) and np.all(out[1] == 0)
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_batch_cols_check_refusals(dtype):
+    M, U, Z = np.zeros((6, 8), dtype), np.zeros((2, 6), dtype), np.zeros((2, 8), dtype)
+    bad = {
+        "k must be in": lambda: _lib.batch_cols_check(M, 8, np.zeros((17, 6), dtype), np.zeros((17, 8), dtype), [0]),
+        "nact must be in": lambda: _lib.batch_cols_check(M, 8, U, Z, [0, 1, 0]),
+        "act entry repeats": lambda: _lib.batch_cols_check(M, 8, U, Z, [0, 0]),
+        "act entry out of range": lambda: _lib.batch_cols_check(M, 8, U, Z, [-1]),
+        "ldm must be": lambda: _lib.batch_cols_check(M, 9, U, Z, [0]),
+        "ldu must be": lambda: _lib.batch_cols_check(M, 8, U[:, :5], Z, [0]),
+        "ldz must be": lambda: _lib.batch_cols_check(M, 8, U, Z[:, :7], [0]),
+    }
+    for msg, call in bad.items():
+        with pytest.raises(RuntimeError, match=msg):
+            call()
+        assert msg in _lib.last_error()
+    M[:] = 1
+    U[:] = 3
+    out = _valid_call_runs_or_lacks_a_device(lambda: _lib.batch_cols_check(M, 7, U, Z, [1]))
+    if out is not None:
+        Zo, nrb, rpb = out
+        assert np.all(Zo[1, :7] == 18) and Zo[1, 7] == 0 and np.all(Zo[0] == 0) and (nrb, rpb) == (1, 16)

@@ -217,9 +217,9 @@ def test_sinkhorn_knopp_stationarity_probe_small_shapes(shape, monkeypatch):
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
 def test_wavefront_sum_in_the_alu_is_the_butterfly_bit_for_bit(dtype):
-    """csrc/reduce.h: dev::wave_sum (v_permlane32_swap, v_permlane16_swap, four DPP adds) against the same tree
-    through __shfl_xor -- every lane of every wavefront, values of mixed sign and magnitude so that the order of
-    the additions shows in the last bits."""
+    """csrc/reduce.h: dev::wave_sum_valu (v_permlane32_swap, v_permlane16_swap, four DPP adds; the fp32 tree of
+    stream_rows2_pf_kernel, and wave_sum itself for fp64) against the same tree through __shfl_xor -- every lane of
+    every wavefront, values of mixed sign and magnitude so that the order of the additions shows in the last bits."""
     from pogs_amd import _lib
     rng = np.random.default_rng(5)
     v = (rng.standard_normal(64 * 4096) * np.exp(rng.uniform(-12, 12, 64 * 4096))).astype(dtype)

@@ -73,3 +73,25 @@ def test_counts_and_shapes_raise_before_the_library(no_library):
         pogs_amd.solve_many([], [], [])                                   # no matrices
     with pytest.raises(ValueError):
         pogs_amd.solve_many(A, [f] * 3, [g] * 3, dtype=np.int32)          # dtype
+
+
+def test_many_setup_check_refusals():
+    A = np.ones((2, 6, 4))
+    bad = {
+        "k must be >= 1": lambda: _lib.many_setup_check(np.ones((0, 6, 4))),
+        "unknown ord": lambda: _lib.many_setup_check(A, ord=7),
+        "m and n must be >= 1": lambda: _lib.many_setup_check(np.ones((1, 0, 4))),
+        "MIN_DIM_MAX": lambda: _lib.many_setup_check(np.ones((1, 513, 513), np.float32)),
+        "MAX_DIM_MAX": lambda: _lib.many_setup_check(np.ones((1, 16385, 1), np.float32)),
+    }
+    for msg, call in bad.items():
+        with pytest.raises(RuntimeError, match=msg):
+            call()
+        assert msg in _lib.last_error()
+    rng = np.random.default_rng(0)
+    try:
+        out = _lib.many_setup_check(rng.standard_normal((2, 6, 4)))
+    except RuntimeError as e:        # no device here: the call got past every argument check
+        assert "HIP error" in str(e), str(e)
+    else:
+        assert np.all(np.isfinite(out["W"])) and np.all(out["nrmA"] > 0)

@@ -101,3 +101,34 @@ def test_solve_batch_routes_by_handle_type(monkeypatch, sparse):
     assert called.calls[0][1] == [1.0 + j for j in range(16)]
     assert called.calls[1][1] == [17.0, 18.0, 19.0, 20.0, 21.0]
     assert len(res) == 21 and all(r["iterations"] == 7 and r["x"].shape == (n,) for r in res)
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_sp_batch_spmv_check_refusals(dtype):
+    ptr, ind, val = np.array([0, 2, 2, 3]), np.array([0, 4, 1]), np.array([1, 2, 3], dtype)
+    X, Y = np.ones((2, 5), dtype), np.zeros((2, 3), dtype)
+    bad = {
+        "k must be in": lambda: _lib.sp_batch_spmv_check(ptr, ind, val, 5, np.ones((17, 5), dtype),
+                                                         np.zeros((17, 3), dtype), [0]),
+        "nact must be in": lambda: _lib.sp_batch_spmv_check(ptr, ind, val, 5, X, Y, [0, 1, 1]),
+        "act entry repeats": lambda: _lib.sp_batch_spmv_check(ptr, ind, val, 5, X, Y, [1, 1]),
+        "act entry out of range": lambda: _lib.sp_batch_spmv_check(ptr, ind, val, 5, X, Y, [2]),
+        "must not decrease": lambda: _lib.sp_batch_spmv_check(np.array([0, 2, 1, 3]), ind, val, 5, X, Y, [0]),
+        "ptr\\[0\\] must be 0": lambda: _lib.sp_batch_spmv_check(np.array([1, 2, 2, 3]), ind, val, 5, X, Y, [0]),
+        "column index out of range": lambda: _lib.sp_batch_spmv_check(ptr, np.array([0, 5, 1]), val, 5, X, Y, [0]),
+        "ldx must be": lambda: _lib.sp_batch_spmv_check(ptr, ind, val, 5, X[:, :4], Y, [0]),
+        "ldy must be": lambda: _lib.sp_batch_spmv_check(ptr, ind, val, 5, X, Y[:, :2], [0]),
+        "ldin must be": lambda: _lib.sp_batch_spmv_check(ptr, ind, val, 5, X, Y, [0], beta=1.0,
+                                                         yin=np.zeros((2, 2), dtype)),
+        "num_cu must be": lambda: _lib.sp_batch_spmv_check(ptr, ind, val, 5, X, Y, [0], num_cu=-1),
+    }
+    for msg, call in bad.items():
+        with pytest.raises(RuntimeError, match=msg):
+            call()
+        assert msg.replace("\\", "") in _lib.last_error()
+    try:
+        Yo, _, geom = _lib.sp_batch_spmv_check(ptr, ind, val, 5, X, Y, [1])
+    except RuntimeError as e:        # no device here: the call got past every argument check
+        assert "HIP error" in str(e), str(e)
+    else:
+        assert list(Yo[1]) == [3, 0, 3] and np.all(Yo[0] == 0) and geom[0] == 4
