@@ -1,11 +1,19 @@
 """Benchmark of the hot path: ADMM iterations/s of the graph-form solve on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config c2|c3|c4]
+    python bench.py --gpus N --steps K --warmup W [--config c2|c3|c4|c2f64] [--full] [--dump-outputs DIR]
 
 With N > 1 and no launcher in the environment the script re-executes itself under
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1`
 (one rank per GPU, RCCL over xGMI); under a launcher (RANK / WORLD_SIZE set) it runs as
 that rank.
+
+A plain run does only what the headline figure needs: it sets the workload up (inputs in HBM, the
+solver handle, one cold solve), runs the W warm-up and K timed steps, writes --dump-outputs and prints
+the line.  With --dump-outputs and without --config it runs c3, c4 and c2f64 the same way after c2, since
+their last steps' outputs are part of what it writes.  --full adds everything else described below, after
+the timed steps: the secondary workloads, `parity_vs_reference`, `cpu_baseline`, `handle_cycles`,
+`exact_setup`, `one_shot_host_call`, the measured read peak and the live counter passes.  The inputs of
+every workload of a run are generated on the host side by side before the first setup (prefetch_inputs).
 
 Workloads (BASELINE.json `configs`); rows are PER GPU ("weak" scaling):
   c2 (default, the metric's configuration): solve_lasso, dense fp32, A = 100000 x 10000 per
@@ -20,7 +28,7 @@ Workloads (BASELINE.json `configs`); rows are PER GPU ("weak" sc
 At N = 1 every workload is the problem of a committed fixture of the COMPILED REFERENCE's own
 solution (tests/golden/c2_reference.npz, c3_reference.npz, c4_reference.npz: numpy PCG64
 generators of pogs_amd/synth.py, regenerated here bit for bit and checked against the fixture's
-checksums), so each line carries `parity_vs_reference`.  At N > 1 every rank draws its rows on its
+checksums), so a --full line carries `parity_vs_reference`.  At N > 1 every rank draws its rows on its
 device (torch, seed 1000 + rank; x_true shared): the shards are row ranges of ONE problem, which
 rank 0 regenerates whole and -- when it fits one GPU -- solves unsharded after the timed region;
 `parity_vs_reference` then holds the sharded solution against that solve (the unsharded engine is
@@ -31,7 +39,7 @@ sums, over-relaxation, projection, residual bookkeeping, dual update, adaptive r
 residuals whenever the reference would evaluate them); when a solve converges the next step
 starts the next solve from the cold start, so K steps are K genuine iterations.  The one-time
 setup (equilibration, norm estimate, Gram + Cholesky / blocked SpMV layout) is outside the
-timed region (init_s); a complete cold solve is reported as time_to_converge_s, and
+timed region (init_s); a complete cold solve is reported as time_to_converge_s, and with --full
 `handle_cycles` repeats create / solve / destroy five times (what a caller of the one-shot ABI
 pays per call, src/interface_c/pogs_c.cpp:19-20) and reports every cycle and the slowest.
 
@@ -45,17 +53,18 @@ section 8(d)): a K that spans whole solves measures that, a shorter one the stre
 
 Inputs are resident in HBM when the timed region starts.  The JSON line carries `roofline`
 (the dominant kernel, timed with HIP events on the solver's stream over the timed region;
-`roofline.traffic` of the headline workload is MEASURED BY THIS RUN at N = 1: after everything
+`roofline.traffic` quotes the committed counter summary profiles/pmc_traffic_<config>.json, and with
+--full that of the headline workload is MEASURED BY THE RUN: after everything
 timed is done the script runs itself twice more for a few steps under `rocprofv3 --pmc
 FETCH_SIZE` / `--pmc WRITE_SIZE` -- about a minute, --no-live-traffic skips it -- and the
-committed counter summaries profiles/pmc_traffic_<config>.json stay in the line as
+committed counter summaries stay in the line as
 `traffic_static`; the secondary workloads quote their committed summaries)
-and `cpu_baseline`: the reference CPU path on the same (A, b, lambda) on this box's
+and, with --full, `cpu_baseline`: the reference CPU path on the same (A, b, lambda) on this box's
 host cores, WHOLE workload (no row sample, nothing scaled) -- at N > 1 rank 0 times it on its OWN
 shard after the timed region (the other ranks wait on sockets) and the line gives the whole problem's
 rate as `value / N`, marked `extrapolated` (every per-iteration term of the reference is linear in m; the
 whole C5 problem is beyond its int-sized views), and `roofline.traffic` is measured on rank 0's GPU.
-The line also carries both roofline peaks (`peak_datasheet`, `peak_measured`: the library's read probe),
+A --full line also carries both roofline peaks (`peak_datasheet`, `peak_measured`: the library's read probe),
 `exact_setup` (the same create + solve with the setup's two shortcuts off), `one_shot_host_call` (the
 reference's entry point with a HOST matrix, and the upload on its own).
 
@@ -79,9 +88,9 @@ profiles/r03_ref_cpu_diagnosis.md) -- c2 capped at --cpu-iters ADMM iterations (
 does not reach the default tolerances there and would run twenty minutes into max_iter;
 --cpu-full runs it to its end), c3 to convergence.  c4: the OpenMP oracle port to convergence
 (the reference's sparse path is single-threaded: 21 minutes).
-Without --config (the driver's invocation) and at N = 1 the c3, c4 and c2f64 workloads are run
-after c2 and attached as `secondary`, each with its own value / roofline / parity (c3, c4 also
-with their CPU leg).
+With --full or --dump-outputs, without --config and at N = 1 the c3, c4 and c2f64 workloads are run
+after c2 and attached as `secondary`, each with its own value / roofline (with --full also parity, and
+c3, c4 with their CPU leg).
 """
 import argparse
 import json
@@ -115,7 +124,12 @@ def parse():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", choices=sorted(CONFIGS), default=None,
-                    help="default: c2 as the headline line, and at --gpus 1 also c3 and c4 as `secondary`")
+                    help="default: c2 as the headline line, and with --full or --dump-outputs at --gpus 1 also c3, c4 "
+                         "and c2f64 as `secondary`")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure, everything else the benchmark measures and checks: the secondary "
+                         "workloads, parity, the CPU baseline, handle cycles, exact setup, one-shot host call, the measured "
+                         "read peak and the live counter passes (the --no-* and --cpu-* options below trim this run)")
     ap.add_argument("--no-secondary", action="store_true")
     # (--rows-per-gpu / --cols: under `python -m torch.distributed.run ... bench.py ARGS` the launcher's own parser
     # reads a bare --m or --n as an ambiguous abbreviation of ITS options -- found by the two-process rehearsal)
@@ -128,7 +142,6 @@ def parse():
     ap.add_argument("--no-live-traffic", action="store_true",
                     help="do not measure roofline.traffic in this run (two short rocprofv3 --pmc passes of the headline "
                          "workload, spawned after the timed part); the committed counter summary is quoted instead")
-    ap.add_argument("--traffic-child", action="store_true", help=argparse.SUPPRESS)   # the spawned pass itself
     ap.add_argument("--cpu-budget-s", type=float, default=600.0,
                     help="time-out of the reference's run of the whole workload (the CPU baseline)")
     ap.add_argument("--cpu-iters", type=int, default=60, help="ADMM iterations of the reference's whole-workload run")
@@ -211,41 +224,75 @@ def torch_rows(cfg, m, n, rank, dev):
     return A, A @ x_true + noise
 
 
-def make_problem(cfg, m, n, rank, dev, world=1):
+def fixture_inputs(cfg, fx):
+    """The problem of a fixture on the host, regenerated bit for bit with the numpy generators of pogs_amd/synth.py
+    and checked against the fixture's checksums: (scipy CSR matrix or dense fp32 matrix, b or labels)."""
+    import numpy as np
+
+    from pogs_amd import synth
+
+    m, n = (int(v) for v in fx["shape"][:2])
+    kind = cfg["kind"]
+    if kind == "csr_lasso":
+        A, b, _ = synth.csr_lasso(m, n, cfg["nnz_per_row"], seed=int(fx["seed"]), dtype=np.float32)
+        chk = np.array([float(A.nnz), float(A.data[::1009].astype(np.float64).sum()),
+                        float(A.indices[::1013].astype(np.float64).sum()), float(np.linalg.norm(b)), float(b[::101].sum())])
+    else:
+        if kind == "dense_lasso":
+            A, b, _ = synth.dense_lasso_rows(m, n, seed=int(fx["seed"]))
+        else:
+            A, b, _ = synth.dense_logistic_rows(m, n, seed=int(fx["seed"]), logit_std=float(fx["logit_std"]))
+        chk = np.array([float(A[::997].astype(np.float64).sum()), float(np.abs(A[:, ::113]).astype(np.float64).sum()),
+                        float(np.linalg.norm(b)) if kind == "dense_lasso" else float(b.sum()), float(b[::101].sum())])
+    if not np.allclose(chk, fx["checksums"], rtol=1e-12, atol=0):
+        raise RuntimeError("the generator no longer reproduces the inputs of %s" % cfg["fixture"])
+    return A, b
+
+
+def prefetch_inputs(env, names):
+    """{workload: fixture_inputs} for every workload of `names` that runs on a fixture's problem (one GPU, the
+    configuration's own size), generated side by side: each generator has its own seed and numpy's generators run
+    without the GIL, so this takes the time of the slowest one instead of the sum.  It is done before the first
+    workload's setup, so nothing runs beside a timed region.  c2f64 shares c2's fp32 matrix (widened on the device)."""
+    import concurrent.futures
+
+    if env.world != 1 or env.args.m or env.args.n:
+        return {}
+    by_fixture = {}
+    for name in names:
+        cfg = CONFIGS[name]
+        fx = load_fixture(cfg)
+        if fx is not None and (cfg["m"], cfg["n"]) == tuple(int(v) for v in fx["shape"][:2]):
+            by_fixture.setdefault(cfg["fixture"], (cfg, fx))
+    if not by_fixture:
+        return {}
+    with concurrent.futures.ThreadPoolExecutor(len(by_fixture)) as ex:
+        futs = {k: ex.submit(fixture_inputs, cfg, fx) for k, (cfg, fx) in by_fixture.items()}
+        made = {k: f.result() for k, f in futs.items()}
+    return {name: made[CONFIGS[name]["fixture"]] for name in names if CONFIGS[name]["fixture"] in made}
+
+
+def make_problem(cfg, m, n, rank, dev, world=1, host=None):
     """Returns (matrix: device tensor or scipy CSR, b or labels, host copy of a dense matrix or None,
     fixture or None).
 
     ONE GPU at the configuration's own size: the problem of the committed fixture of the compiled
-    reference's solution (tests/golden/<cfg["fixture"]>), regenerated bit for bit on the host with
-    the numpy generators of pogs_amd/synth.py and checked against the fixture's checksums -- so the
+    reference's solution (tests/golden/<cfg["fixture"]>), regenerated bit for bit on the host
+    (fixture_inputs; `host`: its result, made ahead by prefetch_inputs) -- so the
     line carries `parity_vs_reference` without a reference run of minutes (c2, c3) to an hour (c4) on
     this box.  Otherwise: torch_rows."""
-    import numpy as np
     import torch
-
-    from pogs_amd import synth
 
     fx = load_fixture(cfg) if world == 1 else None
     if fx is not None and (m, n) == tuple(int(v) for v in fx["shape"][:2]):
-        kind = cfg["kind"]
-        if kind == "csr_lasso":
-            A, b, _ = synth.csr_lasso(m, n, cfg["nnz_per_row"], seed=int(fx["seed"]), dtype=np.float32)
-            chk = np.array([float(A.nnz), float(A.data[::1009].astype(np.float64).sum()),
-                            float(A.indices[::1013].astype(np.float64).sum()), float(np.linalg.norm(b)), float(b[::101].sum())])
-            A_host = None
-        else:
-            if kind == "dense_lasso":
-                A_host, b, _ = synth.dense_lasso_rows(m, n, seed=int(fx["seed"]))
-            else:
-                A_host, b, _ = synth.dense_logistic_rows(m, n, seed=int(fx["seed"]), logit_std=float(fx["logit_std"]))
-            chk = np.array([float(A_host[::997].astype(np.float64).sum()), float(np.abs(A_host[:, ::113]).astype(np.float64).sum()),
-                            float(np.linalg.norm(b)) if kind == "dense_lasso" else float(b.sum()), float(b[::101].sum())])
-            A = torch.from_numpy(A_host).to(dev)
-            if cfg["dtype"] == "f64":
-                A = A.double()      # widened on the device: the entries are the fp32 matrix's, exactly
-                A_host = None       # (no CPU leg for this workload)
-        if not np.allclose(chk, fx["checksums"], rtol=1e-12, atol=0):
-            raise RuntimeError("the generator no longer reproduces the inputs of %s" % cfg["fixture"])
+        A, b = host if host is not None else fixture_inputs(cfg, fx)
+        if cfg["kind"] == "csr_lasso":
+            return A, b, None, fx
+        A_host = A
+        A = torch.from_numpy(A_host).to(dev)
+        if cfg["dtype"] == "f64":
+            A = A.double()      # widened on the device: the entries are the fp32 matrix's, exactly
+            A_host = None       # (no CPU leg for this workload)
         return A, b, A_host, fx
     A, b = torch_rows(cfg, m, n, rank, dev)
     if cfg["dtype"] == "f64" and cfg["kind"] != "csr_lasso":
@@ -519,9 +566,9 @@ def live_traffic(name, kernel_substr, budget_s=150.0, device_index=None):
     try:
         for counter in ("FETCH_SIZE", "WRITE_SIZE"):
             out = os.path.join(tmp, counter)
+            # (a plain run: the workload's setup and steps, nothing of --full)
             cmd = [exe, "--pmc", counter, "--kernel-trace", "--output-format", "csv", "-d", out, "-o", "g", "--",
-                   sys.executable, os.path.abspath(__file__), "--config", name, "--steps", "10", "--warmup", "2",
-                   "--traffic-child", "--no-cpu-baseline", "--no-secondary", "--no-live-traffic"]
+                   sys.executable, os.path.abspath(__file__), "--config", name, "--steps", "10", "--warmup", "2"]
             left = budget_s - (time.time() - t_start)
             if left < 20:
                 return None, "time: budget of the counter passes used up"
@@ -628,6 +675,7 @@ class Env:
         import torch
 
         self.args = args
+        self.host_inputs = {}   # prefetch_inputs: each workload takes its own out (run_config)
         self.rank = int(os.environ.get("RANK", "0"))
         self.world = int(os.environ.get("WORLD_SIZE", "1"))
         self.local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -695,7 +743,8 @@ class Env:
 
 
 def run_config(env, name, with_cpu):
-    """One configuration: build, one cold solve, the timed steps.  Returns the JSON dict on rank 0
+    """One configuration: build, one cold solve, the timed steps (and with --full the extra legs: handle cycles,
+    exact setup, one-shot host call, read peak, parity, CPU baseline).  Returns the JSON dict on rank 0
     (None elsewhere)."""
     import numpy as np
     import torch
@@ -726,7 +775,7 @@ def run_config(env, name, with_cpu):
 
     np_dtype = np.float64 if cfg["dtype"] == "f64" else np.float32
     esize = np.dtype(np_dtype).itemsize
-    A, b, A_host, fixture = make_problem(cfg, m, n, rank, dev, world)
+    A, b, A_host, fixture = make_problem(cfg, m, n, rank, dev, world, env.host_inputs.pop(name, None))
     torch.cuda.synchronize()
 
     if sparse:
@@ -797,7 +846,7 @@ def run_config(env, name, with_cpu):
     # (the reference builds and destroys its solver inside PogsD/PogsS, src/interface_c/pogs_c.cpp:19-20);
     # the library's device pool (pogs_amd/csrc/common.h) is what keeps every cycle at the speed of the fastest
     cycles = None
-    if world == 1 and dist is None and not args.traffic_child:
+    if args.full and world == 1 and dist is None:
         from pogs_amd import _lib as L
 
         p0 = L.pool_stats(local)
@@ -825,7 +874,7 @@ def run_config(env, name, with_cpu):
     # native fp32 MFMA instead of the two-way fp16 split, all 50 Sinkhorn-Knopp passes): what the default saves, and
     # what a caller who wants the reference's setup arithmetic to the last bit pays.
     exact_setup = None
-    if not sparse and cfg["dtype"] == "f32" and world == 1 and dist is None and not args.traffic_child \
+    if args.full and not sparse and cfg["dtype"] == "f32" and world == 1 and dist is None \
             and args.projector == "default":
         saved = {k: os.environ.get(k) for k in ("POGS_AMD_GRAM", "POGS_AMD_SK_FULL")}
         os.environ.update(POGS_AMD_GRAM="fp32", POGS_AMD_SK_FULL="1")   # read at handle creation
@@ -857,7 +906,7 @@ def run_config(env, name, with_cpu):
     # The upload is reported on its own ("H2D separately") from a handle created on the
     # same host buffer, whose t_h2d_s is the copy alone.  Never part of `value`.
     one_shot = None
-    if not sparse and A_host is not None and world == 1 and dist is None and not args.traffic_child \
+    if args.full and not sparse and A_host is not None and world == 1 and dist is None \
             and args.projector == "default" and (m, n) == (cfg["m"], cfg["n"]):
         try:
             torch.cuda.synchronize()
@@ -880,7 +929,7 @@ def run_config(env, name, with_cpu):
     # N > 1: the shards are row ranges of ONE problem; rank 0 regenerates it whole and, when it fits,
     # solves it unsharded -- the sharded solution must land on that solve's
     unsharded = None
-    if world > 1 and not sparse and args.projector == "default":
+    if args.full and world > 1 and not sparse and args.projector == "default":
         bsum = torch.tensor([float(np.asarray(b, np.float64).sum())], dtype=torch.float64, device=env.coll_dev)
         sums = [torch.zeros_like(bsum) for _ in range(world)]
         dist.all_gather(sums, bsum)
@@ -892,7 +941,7 @@ def run_config(env, name, with_cpu):
         env.long_barrier()
 
     line = None
-    if rank == 0 and getattr(env, "peak_measured", None) is None and not args.traffic_child:
+    if rank == 0 and args.full and getattr(env, "peak_measured", None) is None:
         # the measured read ceiling of THIS device next to the data-sheet peak ("state
         # both"): the library's read-bandwidth probe on 4 GB, nothing else running on the GPU
         try:
@@ -978,8 +1027,9 @@ def run_config(env, name, with_cpu):
                          "peak_measured": (getattr(env, "peak_measured", None) or {}).get("gb_per_s"),
                          "frac_of_peak_measured": (achieved / env.peak_measured["gb_per_s"]
                                                    if (getattr(env, "peak_measured", None) or {}).get("gb_per_s") else None),
-                         "peak_measured_how": "PogsAmdReadBandwidth: best of two read-only kernels over 4 GB on this device, "
-                                              "10 launches each (pattern: %s)" % (getattr(env, "peak_measured", None) or {}).get("pattern"),
+                         "peak_measured_how": ("PogsAmdReadBandwidth: best of two read-only kernels over 4 GB on this device, "
+                                               "10 launches each (pattern: %s)" % env.peak_measured.get("pattern")
+                                               if getattr(env, "peak_measured", None) else "not measured (--full measures it)"),
                          "iteration_frac": iteration["frac"],
                          "traffic_source": ("static: %s (rocprofv3 --pmc passes of this command, committed; not "
                                             "measured in this run; %s)"
@@ -1021,7 +1071,7 @@ def run_config(env, name, with_cpu):
             line["one_shot_host_call"] = one_shot
             line["config"]["one_shot_host_call_s"] = one_shot.get("one_shot_host_call_s")
             line["config"]["h2d_s"] = one_shot.get("h2d_s")
-        if fixture is not None:
+        if args.full and fixture is not None:
             try:
                 line["parity_vs_reference"] = parity_from_fixture(cfg, fixture, res)
             except Exception as e:
@@ -1172,18 +1222,22 @@ def main():
     os.environ.setdefault("OMP_NUM_THREADS", str(ob.cpu_quota()))
     env = Env(args)
     head = args.config or "c2"
+    with_cpu = args.full and not args.no_cpu_baseline
+    # without --config, one GPU: c3, c4 (with --full also their CPU legs) and c2 in fp64 under the same clock, with
+    # --full or with --dump-outputs (their last steps' outputs are part of what it writes)
+    secondary = ("c3", "c4", "c2f64") if (args.full or args.dump_outputs) and args.config is None and env.world == 1 \
+        and not args.no_secondary and not (args.m or args.n) and args.projector == "default" else ()
+    env.host_inputs = prefetch_inputs(env, (head,) + secondary)
     # N > 1: rank 0 times the reference on its own shard after the timed region (cpu_baseline / extrapolate_cpu)
-    line = run_config(env, head, with_cpu=not args.no_cpu_baseline)
-    # the driver's invocation (no --config, one GPU): c3, c4 (with their CPU legs) and c2 in fp64 under the same clock
-    if args.config is None and env.world == 1 and not args.no_secondary and not (args.m or args.n) \
-            and args.projector == "default":
+    line = run_config(env, head, with_cpu=with_cpu)
+    if secondary:
         keep = ("metric", "value", "unit", "dtype", "ms_per_step", "steps", "steps_cover", "timed_iterations", "config",
                 "roofline", "time_to_converge_s", "init_s", "handle_cycles", "solve_iterations", "solve_status", "setup_ms", "gram_tflops",
                 "parity_vs_reference", "cpu_baseline", "exact_setup", "time_to_converge_exact_setup_s", "one_shot_host_call")
         sec = {}
-        for name in ("c3", "c4", "c2f64"):
+        for name in secondary:
             try:
-                d = run_config(env, name, with_cpu=not args.no_cpu_baseline)
+                d = run_config(env, name, with_cpu=with_cpu)
                 sec[name] = {k: d[k] for k in keep if k in d}
             except Exception as e:
                 sec[name] = {"value": None, "error": repr(e)[:300]}
@@ -1192,7 +1246,7 @@ def main():
     # roofline.traffic of the headline workload from counters collected NOW (everything timed is done; the
     # committed summary stays in the line as `traffic_static` for comparison)
     # (N > 1: rank 0 alone, on its own GPU, with the shard's size -- the other ranks wait in long_barrier below)
-    if line is not None and not args.no_live_traffic and not args.traffic_child \
+    if line is not None and args.full and not args.no_live_traffic \
             and not (args.m or args.n) and args.projector == "default":
         rf = line["roofline"]
         if time.time() - t_main > LIVE_TRAFFIC_LATEST_START_S:

@@ -2,7 +2,7 @@
 # Development aid: A / B of ONE library under environment settings, alternating on one box.
 #   ab_env.sh "<bench.py arguments>" <reps> "<ENV=a ...>" "<ENV=b ...>" ...      ("-" = no extra environment)
 R=${GRAFT_REPO_ROOT:-/root/repo}
-args=$1; reps=$2; shift 2
+args="$1 --full"; reps=$2; shift 2
 cd $R
 python -c 'import torch; torch.zeros(1, device="cuda")' > /dev/null 2>&1
 for rep in $(seq 1 $reps); do

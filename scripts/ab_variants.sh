@@ -4,7 +4,7 @@
 # a tag names pogs_amd/variants/libpogs_amd_<tag>.so (scripts/build_variant.py); "base" is the regular build.
 # Prints per run: it/s, the dominant kernel's mean launch time, iterations of the solve, rel_x against the fixture.
 R=${GRAFT_REPO_ROOT:-/root/repo}
-args=$1; reps=$2; shift 2
+args="$1 --full"; reps=$2; shift 2
 cd $R
 cp pogs_amd/libpogs_amd.so /tmp/base.so
 python -c 'import torch; torch.zeros(1, device="cuda")' > /dev/null 2>&1

@@ -1,10 +1,12 @@
-"""The driver's bench command, exercised every round: the default invocation (c2 headline line with
-`secondary` c3 / c4 / c2f64) and the same workloads through the RCCL code path with a one-rank communicator
-(POGS_AMD_FORCE_DIST=1) -- the exact command the driver scales to N = 2, 4, 8."""
+"""The driver's bench command, exercised every round: the plain invocation (the c2 headline line alone), the
+--full one (c2 with `secondary` c3 / c4 / c2f64 and every extra leg) and the same workloads through the RCCL code
+path with a one-rank communicator (POGS_AMD_FORCE_DIST=1) -- the exact command the driver scales to N = 2, 4, 8
+(SURVEY.md section 8(e))."""
 import json
 import os
 import subprocess
 import sys
+import time
 
 import pytest
 
@@ -37,13 +39,13 @@ def _close(a, b, rel=1e-5):
 
 
 @pytest.fixture(scope="module")
-def plain():
-    """`python bench.py --gpus 1 --steps 20 --warmup 5` as the driver runs it, GPU legs only."""
-    return _bench(["--gpus", "1", "--steps", "20", "--warmup", "5", "--no-cpu-baseline"])
+def full():
+    """`python bench.py --gpus 1 --steps 20 --warmup 5 --full`, GPU legs only."""
+    return _bench(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline"])
 
 
-def test_default_invocation_carries_the_contract_fields_and_the_secondary_workloads(plain):
-    d = plain
+def test_default_invocation_carries_the_contract_fields_and_the_secondary_workloads(full):
+    d = full
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                 "vs_baseline", "dtype", "data", "config", "roofline"):
         assert key in d, key
@@ -112,12 +114,12 @@ def test_default_invocation_carries_the_contract_fields_and_the_secondary_worklo
         assert s["init_s"] <= init_cap and s["time_to_converge_s"] <= ttc_cap, (name, s["init_s"], s["time_to_converge_s"])
 
 
-def test_the_contract_line_is_short_and_carries_every_workloads_figures(plain):
+def test_the_contract_line_is_short_and_carries_every_workloads_figures(full):
     """BENCH_r05.parsed was null: the line had grown to 24 KB and began with `secondary`, the driver keeps an 8 KB
     tail.  The LAST line is now a summary (bench.summary_line): it starts with `metric`, stays under 6 KB, and
     still holds `roofline`, the wall-clock and parity scalars and a short block per secondary workload; the long
     record is the line before it (asserted in _bench) and gpurun_out/bench_detail.json."""
-    d, sm = plain, plain["_summary"]
+    d, sm = full, full["_summary"]
     assert list(sm)[0] == "metric" and len(json.dumps(sm)) < 6000
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                 "vs_baseline", "dtype", "data", "config", "roofline", "time_to_converge_s", "init_s", "parity", "secondary"):
@@ -146,12 +148,55 @@ def test_the_contract_line_is_short_and_carries_every_workloads_figures(plain):
     assert "cpu_baseline" not in sm          # this fixture runs with --no-cpu-baseline (the forced-communicator test has it)
 
 
+def test_plain_invocation_runs_the_headline_workload_alone(full):
+    """`python bench.py --gpus 1 --steps 20 --warmup 5` as the driver runs it: set-up, warm-up, the timed steps and
+    the line, with the same contract fields as the --full line and none of its extra legs."""
+    t0 = time.time()
+    d = _bench(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    wall = time.time() - t0
+    sm = d["_summary"]
+    assert sm["metric"] == full["metric"] and sm["unit"] == "it/s" and sm["higher_is_better"] is True and sm["dtype"] == "f32"
+    assert sm["steps"] == 20 and sm["warmup"] == 5 and d["timed_iterations"] == 20 and d["config"]["name"] == "c2"
+    assert _close(sm["value"], 1e3 / sm["ms_per_step"], 1e-4)
+    assert d["solve_status"] == 0 and d["solve_iterations"] == full["solve_iterations"]
+    for key in ("secondary", "parity_vs_reference", "cpu_baseline", "handle_cycles", "exact_setup", "one_shot_host_call"):
+        assert key not in d, key
+    rf = d["roofline"]
+    assert rf["peak_measured"] is None and "traffic_live" not in rf and "traffic_static" not in rf
+    assert rf["traffic_source"].startswith("static: profiles/pmc_traffic_c2.json"), rf["traffic_source"]
+    # the budget of a plain run outside its steps (about 11 s on one MI355X box; a --full run takes minutes)
+    outside = wall - (20 + 5) * sm["ms_per_step"] / 1e3
+    print("plain run: %.1f s outside its steps" % outside)
+    assert outside < 30.0, outside
+
+
+def test_plain_dump_outputs_cover_every_default_workload(full, tmp_path):
+    """`--dump-outputs` without --config writes the last step's outputs of c2, c3, c4 and c2f64 (the default
+    invocation's workloads), so a plain run with it runs the three others' steps too -- still without any of
+    --full's extra legs, and within the plain run's budget outside its steps."""
+    t0 = time.time()
+    d = _bench(["--gpus", "1", "--steps", "20", "--warmup", "5", "--dump-outputs", str(tmp_path)])
+    wall = time.time() - t0
+    want = {"%s_%s.npy" % (c, k) for c in ("c2", "c3", "c4", "c2f64") for k in ("x", "y", "l", "mu", "optval")}
+    assert set(os.listdir(tmp_path)) == want, sorted(os.listdir(tmp_path))
+    sec = d["secondary"]
+    assert set(sec) == {"c3", "c4", "c2f64"} and all(s["timed_iterations"] == 20 for s in sec.values()), sec
+    for name, s in [("c2", d)] + sorted(sec.items()):
+        for key in ("parity_vs_reference", "cpu_baseline", "handle_cycles", "exact_setup", "one_shot_host_call"):
+            assert key not in s, (name, key)
+        ref = full if name == "c2" else full["secondary"][name]
+        assert s["solve_status"] == 0 and s["solve_iterations"] == ref["solve_iterations"], (name, s["solve_iterations"])
+    outside = wall - (20 + 5) * (d["ms_per_step"] + sum(s["ms_per_step"] for s in sec.values())) / 1e3
+    print("plain run with --dump-outputs: %.1f s outside its steps" % outside)
+    assert outside < 30.0, outside
+
+
 def test_forced_communicator_line_is_contract_complete():
-    """The first multi-GPU line must not be the first time its extra legs run: the driver's
+    """The first multi-GPU line must not be the first time its extra legs run: the --full
     command through the one-rank RCCL path carries `cpu_baseline`, a `roofline.traffic` measured in the run (the
     counter passes' children must not inherit the rendezvous / forced-communicator environment),
     `parity_vs_reference` and `config.rccl_nranks == 1`."""
-    d = _bench(["--gpus", "1", "--steps", "20", "--warmup", "5", "--no-secondary", "--cpu-best-only"],
+    d = _bench(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--no-secondary", "--cpu-best-only"],
                {"POGS_AMD_FORCE_DIST": "1"}, timeout=900)
     assert d["config"]["rccl_nranks"] == 1 and d["n_gpus"] == 1 and d["config"]["name"] == "c2"
     cb = d["cpu_baseline"]
@@ -171,7 +216,7 @@ def test_forced_communicator_line_is_contract_complete():
 
 
 @pytest.mark.parametrize("cfg", ["c2", "c4"])
-def test_one_rank_rccl_path_runs_the_bench_command_at_the_plain_speed(plain, cfg):
+def test_one_rank_rccl_path_runs_the_bench_command_at_the_plain_speed(full, cfg):
     """rccl_nranks is what ncclCommCount reports; one rank's collectives are no-ops, so the line must
     come out within a few per cent of the plain run -- for c4 too since round 4: row shards run the
     device-resident CGLS loop with ONE grouped all-reduce per CG step on the stream (t = A^T q and the
@@ -179,7 +224,7 @@ def test_one_rank_rccl_path_runs_the_bench_command_at_the_plain_speed(plain, cfg
     alternating, -1.5 / -2.2 / -1.9 % against the plain run (scripts/c4_one_rank.sh)."""
     d = _bench(["--gpus", "1", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-live-traffic", "--config", cfg],
                {"POGS_AMD_FORCE_DIST": "1"})
-    ref = plain if cfg == "c2" else plain["secondary"][cfg]
+    ref = full if cfg == "c2" else full["secondary"][cfg]
     assert d["config"]["rccl_nranks"] == 1 and d["n_gpus"] == 1
     assert d["solve_status"] == 0 and abs(d["solve_iterations"] - ref["solve_iterations"]) <= 3
     # the two runs are separate processes timing 20-step windows: c4's one-rank line was seen at -1.5 % .. -6.8 %
@@ -238,7 +283,7 @@ def test_two_process_rehearsal_of_the_launcher_path():
     t0 = time.time()
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-                        "--gpus", "2", "--steps", "20", "--warmup", "5", "--rows-per-gpu", "12000", "--cols", "1500"],
+                        "--gpus", "2", "--steps", "20", "--warmup", "5", "--full", "--rows-per-gpu", "12000", "--cols", "1500"],
                        capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     wall = time.time() - t0
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
