@@ -399,6 +399,32 @@ int PogsAmdSpBatchSpmvCheck(int dtype, int nrows, int ncols, const int *ptr, con
  * K x K row-major, W = L^-1 in its lower triangle for L L^T = I + A_eq^T A_eq (m > n) or I + A_eq A_eq^T. */
 int PogsAmdManySetupCheck(int dtype, enum ORD ord, int k, size_t m, size_t n, const void *A, int mem, void *A_eq,
                           void *d, void *e, double *nrmA, void *W);
+/* Diagnostics of the dense factorisation (DenseSolver::factor: Gram product, Cholesky, L^-1).  HOST arrays of type
+ * dtype, row-major; invalid arguments are refused before any device work, as above. */
+/* G = P^T P for a K-major operand P (kdim rows of k columns, leading dimension lda: what a tall handle stores, and a
+ * wide one, which keeps A^T), by the very function factor() calls, which picks the product from (kdim, k, CU count):
+ * native fp32 / fp64 MFMA tiles, split-K into slabs, two-level accumulation, or the fp16 split on the 128 or 256 tile.
+ * (The row-major operand form of the native product cannot be reached from factor() and is not offered.)  lda: a
+ * multiple of VEC, >= k; P's columns >= k are never read.  num_cu: 0 = the device's.  force: 0 = as a solve would
+ * choose (the environment included), 1 = POGS_AMD_GRAM=fp32, 128 / 256 = POGS_AMD_GRAM_TILE (like the variable it
+ * only picks the tile where the fp16 split is the product of the shape).  G: k x ldg (ldg >= k), uploaded before and
+ * downloaded after: the lower 128-tiles are written (whole diagonal tiles, so G is symmetric inside them), entries
+ * above them come back as they were.  info (8 ints) = {path (0 native, 1 fp16 split), tile, ksplit, kchunk, kacc,
+ * K units, rows per unit, 1 if the tiles ran in gram_tile_order}; ksplit, kchunk and kacc are 0 on path 1. */
+int PogsAmdGramCheck(int dtype, int kdim, int k, const void *P, size_t lda, int num_cu, int force, void *G, size_t ldg,
+                     int *info);
+/* For a symmetric positive definite H (n x ldh, n >= 1; only the lower triangle is read) the sequence of factor()
+ * after the diagonal shift: four zeroed slabs of n x ld, ld = round_up(n, VEC), H into the first, cholesky_lower,
+ * trtri_lower, launch_transpose.  L (L L^T = H), W = L^-1 and U = W^T come back as the slabs hold them, rows of
+ * min(ldo, ld) columns at stride ldo (ldo >= n): the strict upper triangle of L is what H held there, that of W and
+ * the strict lower one of U are zero, and so are the columns n .. ld.  An H that is not positive definite is no
+ * error: the square root of the bad pivot is NaN, and NaN spreads from there (the reference's
+ * linalg_cholesky_decomp reports an error instead). */
+int PogsAmdCholCheck(int dtype, int n, const void *H, size_t ldh, void *L, void *W, void *U, size_t ldo);
+/* W = L^-1 and U = W^T of a dense handle with the direct projector, L L^T = I + A_eq^T A_eq (m > n) or
+ * I + A_eq A_eq^T: HOST outputs of k x k, k = min(m, n), either may be NULL.  On row shards every rank holds the
+ * factor of the whole matrix.  POGS_ERROR on a sparse handle and on one that runs the CGLS projector. */
+int PogsAmdGetFactor(const PogsAmdSolver *s, void *W, void *U);
 /* The Norm2Est start vector (reference: gsl::rand, src/cpu/include/gsl/gsl_rand.h:8-16). */
 int PogsAmdRandUniform(int dtype, size_t n, void *out_host);
 

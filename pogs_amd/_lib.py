@@ -162,6 +162,11 @@ lib.PogsAmdSpBatchSpmvCheck.argtypes = [c_int, c_int, c_int, c_void_p, c_void_p,
                                         c_int, c_void_p]
 lib.PogsAmdManySetupCheck.argtypes = [c_int, c_int, c_int, c_size_t, c_size_t, c_void_p, c_int, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_void_p]
+lib.PogsAmdGramCheck.argtypes = [c_int, c_int, c_int, c_void_p, c_size_t, c_int, c_int, c_void_p, c_size_t, c_void_p]
+lib.PogsAmdCholCheck.argtypes = [c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_size_t]
+lib.PogsAmdGetFactor.argtypes = [c_void_p, c_void_p, c_void_p]
+GRAM_AUTO, GRAM_NATIVE, GRAM_TILE_128, GRAM_TILE_256 = 0, 1, 128, 256   # `force` of PogsAmdGramCheck
+GRAM_INFO = ("path", "tile", "ksplit", "kchunk", "kacc", "units", "unit_rows", "tile_map")
 
 
 class PogsAmdPoolInfo(ctypes.Structure):
@@ -198,7 +203,7 @@ ABI_SYMBOLS = [
     "PogsAmdPoolStats", "PogsAmdPoolTrim",
     "PogsAmdProxEval", "PogsAmdFuncEval", "PogsAmdProjSubgradEval", "PogsAmdGetEquil", "PogsAmdProject", "PogsAmdMul", "PogsAmdRandUniform",
     "PogsAmdReadBandwidth", "PogsAmdWaveSumCheck", "PogsAmdBatchRowsCheck", "PogsAmdBatchColsCheck",
-    "PogsAmdSpBatchSpmvCheck", "PogsAmdManySetupCheck",
+    "PogsAmdSpBatchSpmvCheck", "PogsAmdManySetupCheck", "PogsAmdGramCheck", "PogsAmdCholCheck", "PogsAmdGetFactor",
 ]
 
 
@@ -326,6 +331,49 @@ def many_setup_check(A, ord=ROW_MAJ):
                                  out["W"].ctypes.data) != 0:
         raise RuntimeError(last_error())
     return out
+
+
+def gram_check(P, k, G, force=GRAM_AUTO, num_cu=0):
+    """(G, info): G[:k, :k] = P[:, :k]^T P[:, :k] on the lower 128-tiles by the Gram phase of the dense factorisation
+    (include/pogs_amd.h: PogsAmdGramCheck).  P: kdim x lda, G: k x ldg; info: dict of GRAM_INFO.  Returns a new
+    array; G itself is not changed."""
+    import numpy as np
+    P = np.ascontiguousarray(P)
+    G = np.array(G, order="C", copy=True)
+    code = _dtype_code(P, G)
+    if P.ndim != 2 or G.ndim != 2 or G.shape[0] != k:
+        raise ValueError("P (kdim, lda), G (k, ldg)")
+    info = np.zeros(8, dtype=np.int32)
+    if lib.PogsAmdGramCheck(code, P.shape[0], k, P.ctypes.data, P.shape[1], num_cu, force, G.ctypes.data, G.shape[1],
+                            info.ctypes.data) != 0:
+        raise RuntimeError(last_error())
+    return G, dict(zip(GRAM_INFO, (int(v) for v in info)))
+
+
+def chol_check(H, ldo=None):
+    """(L, W, U) of the dense factorisation's Cholesky, inverse and transpose on H (n x ldh, lower triangle read):
+    L L^T = H, W = L^-1, U = W^T, each n x ldo as the device slabs hold them (include/pogs_amd.h: PogsAmdCholCheck;
+    ldo defaults to n).  The outputs start as NaN, so columns the entry does not return stay NaN."""
+    import numpy as np
+    H = np.ascontiguousarray(H)
+    code = _dtype_code(H)
+    if H.ndim != 2 or H.shape[1] < H.shape[0]:
+        raise ValueError("H (n, ldh >= n)")
+    n = H.shape[0]
+    ldo = n if ldo is None else ldo
+    L, W, U = (np.full((n, ldo), np.nan, H.dtype) for _ in range(3))
+    if lib.PogsAmdCholCheck(code, n, H.ctypes.data, H.shape[1], L.ctypes.data, W.ctypes.data, U.ctypes.data, ldo) != 0:
+        raise RuntimeError(last_error())
+    return L, W, U
+
+
+def get_factor(handle, k, dtype):
+    """(W, U) of a live dense handle (include/pogs_amd.h: PogsAmdGetFactor): k x k, k = min(m, n)."""
+    import numpy as np
+    W, U = np.zeros((k, k), dtype), np.zeros((k, k), dtype)
+    if lib.PogsAmdGetFactor(handle, W.ctypes.data, U.ctypes.data) != 0:
+        raise RuntimeError(last_error())
+    return W, U
 
 
 def last_error():

@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "engine.h"
+#include "factor_check.h"
 #include "many_kernels.h"
 #include "sparse_batch_kernels.h"
 #include "prox.h"
@@ -637,6 +638,40 @@ int PogsAmdManySetupCheck(int dtype, enum ORD ord, int k, size_t m, size_t n, co
                           void *d, void *e, double *nrmA, void *W) {
   return guarded([&]() {
     many_setup_check(dtype, static_cast<int>(ord), k, m, n, A, mem, A_eq, d, e, nrmA, W);
+    return 0;
+  });
+}
+
+int PogsAmdGramCheck(int dtype, int kdim, int k, const void *P, size_t lda, int num_cu, int force, void *G, size_t ldg,
+                     int *info) {
+  return guarded([&]() {
+    POGS_CHECK(dtype == POGS_AMD_F32 || dtype == POGS_AMD_F64, "unknown dtype");
+    if (dtype == POGS_AMD_F32)
+      gram_check<float>(kdim, k, static_cast<const float *>(P), lda, num_cu, force, static_cast<float *>(G), ldg, info);
+    else
+      gram_check<double>(kdim, k, static_cast<const double *>(P), lda, num_cu, force, static_cast<double *>(G), ldg, info);
+    return 0;
+  });
+}
+
+int PogsAmdCholCheck(int dtype, int n, const void *H, size_t ldh, void *L, void *W, void *U, size_t ldo) {
+  return guarded([&]() {
+    POGS_CHECK(dtype == POGS_AMD_F32 || dtype == POGS_AMD_F64, "unknown dtype");
+    if (dtype == POGS_AMD_F32)
+      chol_check<float>(n, static_cast<const float *>(H), ldh, static_cast<float *>(L), static_cast<float *>(W),
+                        static_cast<float *>(U), ldo);
+    else
+      chol_check<double>(n, static_cast<const double *>(H), ldh, static_cast<double *>(L), static_cast<double *>(W),
+                         static_cast<double *>(U), ldo);
+    return 0;
+  });
+}
+
+int PogsAmdGetFactor(const PogsAmdSolver *s, void *W, void *U) {
+  return guarded([&]() {
+    POGS_CHECK(s && s->impl, "null solver");
+    DeviceGuard guard(s->impl->device());
+    const_cast<PogsAmdSolver *>(s)->impl->get_factor(W, U);
     return 0;
   });
 }

@@ -27,6 +27,7 @@
 #include "engine.h"
 #include "fused_cols.h"
 #include "gemm.h"
+#include "gram_phase.h"
 #include "ops.h"
 #include "reduce.h"
 #include "stream.h"
@@ -259,6 +260,15 @@ class DenseSolver final : public SolverBase {
     if (d) POGS_HIP_CHECK(hipMemcpy(d, d_.p, m_ * sizeof(T), hipMemcpyDeviceToHost));
     if (e) POGS_HIP_CHECK(hipMemcpy(e, e_.p, n_ * sizeof(T), hipMemcpyDeviceToHost));
     if (nrmA) *nrmA = nrmA_;
+  }
+
+  // W = L^-1 and U = W^T as the solves read them: k x k row-major on the host, k = min(m, n).
+  void get_factor(void *W, void *U) override {
+    POGS_CHECK(!use_cgls_ && Wp_ && Up_, "no factor: the handle runs the CGLS projector");
+    ctx_.sync();
+    const size_t row = static_cast<size_t>(k_) * sizeof(T), pitch = static_cast<size_t>(k_pad_) * sizeof(T);
+    if (W) POGS_HIP_CHECK(hipMemcpy2D(W, row, Wp_, pitch, row, k_, hipMemcpyDeviceToHost));
+    if (U) POGS_HIP_CHECK(hipMemcpy2D(U, row, Up_, pitch, row, k_, hipMemcpyDeviceToHost));
   }
 
   // (x, y) = Proj_{y = A x}(x0, y0), projector_direct_dense.cpp:122-127.

@@ -682,6 +682,8 @@ struct SolverBase {
   virtual void iterate(unsigned iters, double *seconds, unsigned *solves) = 0;
   virtual void set_warm_start(const void *x0, const void *l0) = 0;
   virtual void get_equil(void *A_eq, void *d, void *e, double *nrmA) = 0;
+  // the dense direct projector's W = L^-1 and U = W^T (HOST, k x k, either may be null)
+  virtual void get_factor(void *, void *) { throw Error("PogsAmdGetFactor needs a dense handle"); }
   virtual void project(const void *x0, const void *y0, double tol, void *x, void *y) = 0;
   virtual void mul(char trans, double alpha, const void *x, double beta, void *y) = 0;
   virtual PogsAmdStats &stats() = 0;

@@ -516,8 +516,10 @@ class Solver:
         code = _lib.F64 if self.dtype == np.float64 else _lib.F32
         opt = _lib.PogsAmdOptions(device=device, projector=projector, profile=int(profile))
         dist_s = None
+        self._m_global = None   # row shards: the rows of the whole matrix
         if dist is not None:
             rank, world, m_global, uid = dist
+            self._m_global = int(m_global)
             dist_s = _lib.PogsAmdDist(rank=rank, world=world, m_global=m_global)
             uid = bytes(uid)
             assert len(uid) == _lib.UNIQUE_ID_BYTES
@@ -693,6 +695,11 @@ class Solver:
         if st != 0:
             raise RuntimeError("pogs_amd: " + _lib.last_error())
         return A_eq, d, e, nrm.value
+
+    def factor(self):
+        """(W, U): W = L^-1 and U = W^T of the direct projector, L L^T = I + A_eq^T A_eq (m > n) or I + A_eq A_eq^T
+        (dense solvers; include/pogs_amd.h: PogsAmdGetFactor)."""
+        return _lib.get_factor(self._h, min(self._m_global or self.m, self.n), self.dtype)
 
     def project(self, x0, y0, tol=1e-8):
         x0 = np.ascontiguousarray(x0, self.dtype)

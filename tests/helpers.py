@@ -155,3 +155,95 @@ def run_sharded_oracle(A, f, g, world, dtype, bounds=None, **solve_kw):
     assert not errors, errors
     assert all(r is not None for r in results)
     return results, bounds
+
+
+# ---- kernels against high-precision references (test_gpu_batch_kernels.py, test_gpu_factor_kernels.py) -----------
+
+def gamma(n, dt, u=None):
+    """gamma_n = n u / (1 - n u); u: the unit roundoff of dt (eps / 2) unless given (eps for an accumulate that truncates)"""
+    u = np.finfo(dt).eps / 2 if u is None else u
+    return n * u / (1 - n * u)
+
+
+def same_bytes(a, b):
+    return np.array_equal(np.ascontiguousarray(a).view(np.uint8), np.ascontiguousarray(b).view(np.uint8))
+
+
+def ints(rng, shape, dt):
+    return rng.integers(-4, 5, shape).astype(dt)
+
+
+def scaled_normal(rng, shape):
+    """standard_normal with rows and columns scaled by 2^-10 .. 2^10"""
+    r, c = shape
+    return rng.standard_normal(shape) * np.exp2(rng.uniform(-10, 10, (r, 1))) * np.exp2(rng.uniform(-10, 10, (1, c)))
+
+
+def hi(a):
+    """the precision of a reference: fp64 for fp32 data, long double for fp64 data"""
+    return np.asarray(a, np.longdouble if a.dtype == np.float64 else np.float64)
+
+
+def within_gamma(got, ref, absref, n, dt):
+    err = np.abs(hi(got) - ref)
+    bar = gamma(n, dt) * absref
+    assert np.all(np.isfinite(got))
+    assert np.all(err <= bar), float(np.max(err - bar))
+
+
+def _w_bars(m, n, dt, gram=True):
+    """Bars of W = L^-1 (L L^T = H = I + G, G = A_eq^T A_eq or A_eq A_eq^T, K = min(m, n), R = max(m, n)).
+
+    ||A_eq||_F^2 = K (the equilibration's normalisation), so 1 <= lambda(H) <= 1 + K: cond(H) <= 1 + K,
+    ||W||_2 <= 1 and ||W||_F^2 = trace(H^-1) <= K, ||L||_F^2 = trace(H) = 2K.
+      Gram (R-term dot products in T):   ||dG||_2 <= ||dG||_F <= gamma_R || |A|^T |A| ||_F <= gamma_R K
+      Cholesky (backward):               L^ L^T = H + dG + dC, ||dC||_2 <= gamma_(K+1) ||L^||_F^2 = gamma_(K+1) 2K
+      inversion (W^ L^ = I + E):         ||E||_2 <= gamma_K ||W^||_F ||L^||_F <= gamma_K sqrt(2) K
+    so the residual R = W^ H W^T - I = (I + E)(I + E)^T - I - W^ (dG + dC) W^T has
+      ||R||_2 <= r := 2 e + e^2 + gamma_R K + 2 gamma_(K+1) K,  e = sqrt(2) gamma_K K,
+    plus its evaluation in fp64 (two products of K-term sums: 2 gamma64_(2K) ||W^||_2^2 ||H||_2 <= 2 gamma64_(2K) (1 + K)).
+    W^ L = T is lower triangular with T T^T = I + R: T is the Cholesky factor of I + R, so T = I + F with
+    ||F||_F <= ||R||_F / (sqrt(2) (1 - ||R||_2)) <= sqrt(K) r / (1 - r), and W^ - W = F W: |W^ - W|_max <= ||F||_F
+    ||W||_2 <= sqrt(K) r / (1 - r), plus the fp64 reference's own error (the same bound with u of fp64).
+    gram=False: H itself is the input (no Gram product in T): the gamma_R K term is left out."""
+    K, R = min(m, n), max(m, n)
+
+    def r_of(d):
+        e = np.sqrt(2) * gamma(K, d) * K
+        return 2 * e + e * e + (gamma(R, d) * K if gram else 0.0) + 2 * gamma(K + 1, d) * K
+
+    r = r_of(dt)
+    r64 = r_of(np.float64)
+    res_bar = r + 2 * gamma(2 * K, np.float64) * (1 + K)
+    w_bar = np.sqrt(K) * (r / (1 - r) + r64 / (1 - r64))
+    return res_bar, w_bar
+
+
+def xmatmul(A, B, slices=4):
+    """A @ B for float64 matrices as a long double array, every entry within about n 2^-76 of (largest |entry| of
+    A's row) x (largest of B's column): error-free slicing (Ozaki's scheme).  Each operand is cut into `slices` pieces
+    of beta bits below its row / column maximum, beta so small that a product of two pieces is a sum of n integers
+    below 2^53 in a common unit -- exact in a float64 BLAS whatever its order of summation; the piece products are
+    then added in long double, smallest first.  (numpy multiplies long double matrices without a BLAS, about a
+    thousand times slower.)"""
+    A, B = np.asarray(A, np.float64), np.asarray(B, np.float64)
+    n = A.shape[1]
+    beta = (53 - int(np.ceil(np.log2(max(n, 2)))) - 1) // 2
+
+    def cut(M, axis):
+        mx = np.max(np.abs(M), axis=axis, keepdims=True)
+        q = np.ceil(np.log2(np.where(mx > 0, mx, 1.0))).astype(np.int64)        # |M| <= 2^q along the axis
+        rem, parts = M.copy(), []
+        for s in range(slices):
+            c = np.ldexp(1.5, q - beta * (s + 1) + 52)       # ulp(c) = 2^(q - beta (s + 1)): adding c rounds to it
+            piece = (rem + c) - c
+            rem = rem - piece                                 # exact
+            parts.append(piece)
+        return parts
+
+    pa, pb = cut(A, 1), cut(B, 0)
+    out = np.zeros((A.shape[0], B.shape[1]), np.longdouble)
+    for tot in range(slices - 1, -1, -1):
+        for i in range(tot + 1):
+            out += pa[i] @ pb[tot - i]
+    return out

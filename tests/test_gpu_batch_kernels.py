@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 import oracle_binding as ob
-from helpers import relerr
+from helpers import _w_bars, gamma, hi, ints, relerr, same_bytes, scaled_normal, within_gamma
 from pogs_amd import _lib
 
 pytestmark = pytest.mark.gpu
@@ -31,37 +31,6 @@ def vec(dt):
 
 def rup(v, a):
     return (v + a - 1) // a * a
-
-
-def gamma(n, dt):
-    u = np.finfo(dt).eps / 2
-    return n * u / (1 - n * u)
-
-
-def same_bytes(a, b):
-    return np.array_equal(np.ascontiguousarray(a).view(np.uint8), np.ascontiguousarray(b).view(np.uint8))
-
-
-def ints(rng, shape, dt):
-    return rng.integers(-4, 5, shape).astype(dt)
-
-
-def scaled_normal(rng, shape):
-    """standard_normal with rows and columns scaled by 2^-10 .. 2^10"""
-    r, c = shape
-    return rng.standard_normal(shape) * np.exp2(rng.uniform(-10, 10, (r, 1))) * np.exp2(rng.uniform(-10, 10, (1, c)))
-
-
-def hi(a):
-    """the precision of a reference: fp64 for fp32 data, long double for fp64 data"""
-    return np.asarray(a, np.longdouble if a.dtype == np.float64 else np.float64)
-
-
-def within_gamma(got, ref, absref, n, dt):
-    err = np.abs(hi(got) - ref)
-    bar = gamma(n, dt) * absref
-    assert np.all(np.isfinite(got))
-    assert np.all(err <= bar), float(np.max(err - bar))
 
 
 def slot_lists(rng, p):
@@ -413,33 +382,6 @@ def test_sp_batch_spmv_isolation_every_kp(dtype):
 # ---- many-problem setup (copy, Sinkhorn-Knopp, scale, norm estimate, Gram, Cholesky, W = L^-1) ---------------------
 
 MANY_SHAPES = [(70, 33), (37, 101), (200, 1), (1, 30), (130, 65), (150, 63), (64, 90), (65, 300), (300, 129)]
-
-
-def _w_bars(m, n, dt):
-    """Bars of W = L^-1 (L L^T = H = I + G, G = A_eq^T A_eq or A_eq A_eq^T, K = min(m, n), R = max(m, n)).
-
-    ||A_eq||_F^2 = K (the equilibration's normalisation), so 1 <= lambda(H) <= 1 + K: cond(H) <= 1 + K,
-    ||W||_2 <= 1 and ||W||_F^2 = trace(H^-1) <= K, ||L||_F^2 = trace(H) = 2K.
-      Gram (R-term dot products in T):   ||dG||_2 <= ||dG||_F <= gamma_R || |A|^T |A| ||_F <= gamma_R K
-      Cholesky (backward):               L^ L^T = H + dG + dC, ||dC||_2 <= gamma_(K+1) ||L^||_F^2 = gamma_(K+1) 2K
-      inversion (W^ L^ = I + E):         ||E||_2 <= gamma_K ||W^||_F ||L^||_F <= gamma_K sqrt(2) K
-    so the residual R = W^ H W^T - I = (I + E)(I + E)^T - I - W^ (dG + dC) W^T has
-      ||R||_2 <= r := 2 e + e^2 + gamma_R K + 2 gamma_(K+1) K,  e = sqrt(2) gamma_K K,
-    plus its evaluation in fp64 (two products of K-term sums: 2 gamma64_(2K) ||W^||_2^2 ||H||_2 <= 2 gamma64_(2K) (1 + K)).
-    W^ L = T is lower triangular with T T^T = I + R: T is the Cholesky factor of I + R, so T = I + F with
-    ||F||_F <= ||R||_F / (sqrt(2) (1 - ||R||_2)) <= sqrt(K) r / (1 - r), and W^ - W = F W: |W^ - W|_max <= ||F||_F
-    ||W||_2 <= sqrt(K) r / (1 - r), plus the fp64 reference's own error (the same bound with u of fp64)."""
-    K, R = min(m, n), max(m, n)
-
-    def r_of(d):
-        e = np.sqrt(2) * gamma(K, d) * K
-        return 2 * e + e * e + gamma(R, d) * K + 2 * gamma(K + 1, d) * K
-
-    r = r_of(dt)
-    r64 = r_of(np.float64)
-    res_bar = r + 2 * gamma(2 * K, np.float64) * (1 + K)
-    w_bar = np.sqrt(K) * (r / (1 - r) + r64 / (1 - r64))
-    return res_bar, w_bar
 
 
 def _many_check(dt, m, n, A):
