@@ -375,7 +375,7 @@ int PogsAmdWaveSumCheck(int dtype, size_t n, const void *in_host, void *alu_host
 /* Y[p][r] = sum_c M[r][c] X[p][c] for r < rows and the problems p of act (the batched solve's launch_batch_rows).
  * M: rows x ldm row-major; ldm, ldx: multiples of VEC, >= cols_pad; ldy >= rows.  tri: 0 full, 1 lower (c <= r),
  * 2 upper (c >= r) triangle of a square M (rows == cols); entries outside the triangle and M's columns >= cols are
- * never used.  Contract of the caller (dense_batch.h keeps it): X[p][c] == 0 for cols <= c < cols_pad. */
+ * never used.  Contract of the caller (batch_admm.h's vectors keep it): X[p][c] == 0 for cols <= c < cols_pad. */
 int PogsAmdBatchRowsCheck(int dtype, int tri, int rows, int cols, const void *M, size_t ldm, int k, const int *act,
                           int nact, const void *X, size_t ldx, void *Y, size_t ldy);
 /* Z[p][c] = sum_r M[r][c] U[p][r] (+ add[p][c] when add is not NULL) for c < cols, Z[p][c] = 0 for

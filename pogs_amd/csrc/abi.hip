@@ -2,6 +2,7 @@
 #include <cmath>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "engine.h"
@@ -331,6 +332,20 @@ FnHost fn_host(const PogsAmdFn *p) {
   POGS_CHECK(p->h || (p->h0 >= 0 && p->h0 <= 15), "function code out of range");
   return f;
 }
+// The k function pairs of a multi-problem entry point (first: every f, second: every g), after its null checks;
+// `what`: "batched solve" / "many-problem solve", the prefix of its messages.
+std::pair<std::vector<FnHost>, std::vector<FnHost>> fn_hosts(const std::string &what, int k, const PogsAmdFn *f,
+                                                             const PogsAmdFn *g, const void *x,
+                                                             const unsigned *final_iter, const int *status) {
+  POGS_CHECK(f && g, (what + ": null function descriptions").c_str());
+  POGS_CHECK(x && final_iter && status, (what + ": x, final_iter and status must not be NULL").c_str());
+  std::pair<std::vector<FnHost>, std::vector<FnHost>> fg;
+  for (int j = 0; j < k; ++j) {
+    fg.first.push_back(fn_host(&f[j]));
+    fg.second.push_back(fn_host(&g[j]));
+  }
+  return fg;
+}
 }  // namespace
 
 int PogsAmdSolveFn(PogsAmdSolver *s, const PogsAmdFn *f, const PogsAmdFn *g, double rho, double abs_tol, double rel_tol,
@@ -352,15 +367,9 @@ int PogsAmdSolveBatchFn(PogsAmdSolver *s, int k, const PogsAmdFn *f, const PogsA
   return guarded([&]() {
     POGS_CHECK(s && s->impl, "null solver");
     POGS_CHECK(k >= 1 && k <= POGS_AMD_BATCH_MAX, "batched solve: k must be in [1, POGS_AMD_BATCH_MAX]");
-    POGS_CHECK(f && g, "batched solve: null function descriptions");
-    POGS_CHECK(x && final_iter && status, "batched solve: x, final_iter and status must not be NULL");
+    const auto fg = fn_hosts("batched solve", k, f, g, x, final_iter, status);
     DeviceGuard guard(s->impl->device());
-    std::vector<FnHost> fh, gh;
-    for (int j = 0; j < k; ++j) {
-      fh.push_back(fn_host(&f[j]));
-      gh.push_back(fn_host(&g[j]));
-    }
-    s->impl->solve_batch(k, fh.data(), gh.data(), rho,
+    s->impl->solve_batch(k, fg.first.data(), fg.second.data(), rho,
                          make_params(1.0, abs_tol, rel_tol, max_iter, verbose, adaptive_rho, gap_stop),
                          BatchOut{x, y, l, mu, optval, final_iter, status});
     return 0;
@@ -374,15 +383,9 @@ int PogsAmdSolveBatchSparseFn(PogsAmdSolver *s, int k, const PogsAmdFn *f, const
   return guarded([&]() {
     POGS_CHECK(s && s->impl, "null solver");
     POGS_CHECK(k >= 1 && k <= POGS_AMD_BATCH_MAX, "batched solve: k must be in [1, POGS_AMD_BATCH_MAX]");
-    POGS_CHECK(f && g, "batched solve: null function descriptions");
-    POGS_CHECK(x && final_iter && status, "batched solve: x, final_iter and status must not be NULL");
+    const auto fg = fn_hosts("batched solve", k, f, g, x, final_iter, status);
     DeviceGuard guard(s->impl->device());
-    std::vector<FnHost> fh, gh;
-    for (int j = 0; j < k; ++j) {
-      fh.push_back(fn_host(&f[j]));
-      gh.push_back(fn_host(&g[j]));
-    }
-    s->impl->solve_batch_sparse(k, fh.data(), gh.data(), rho,
+    s->impl->solve_batch_sparse(k, fg.first.data(), fg.second.data(), rho,
                                 make_params(1.0, abs_tol, rel_tol, max_iter, verbose, adaptive_rho, gap_stop),
                                 BatchOut{x, y, l, mu, optval, final_iter, status});
     return 0;
@@ -396,19 +399,13 @@ int PogsAmdSolveManyFn(int dtype, enum ORD ord, int k, size_t m, size_t n, const
                        int *status) {
   return guarded([&]() {
     POGS_CHECK(k >= 1, "many-problem solve: k must be >= 1");
-    POGS_CHECK(f && g, "many-problem solve: null function descriptions");
-    POGS_CHECK(x && final_iter && status, "many-problem solve: x, final_iter and status must not be NULL");
     const int projector = opt ? opt->projector : POGS_AMD_PROJ_DEFAULT;
     POGS_CHECK(projector == POGS_AMD_PROJ_DEFAULT || projector == POGS_AMD_PROJ_DIRECT,
                "many-problem solve: only the direct projector is supported (CGLS refused)");
     const int device = opt ? opt->device : -1;
+    const auto fg = fn_hosts("many-problem solve", k, f, g, x, final_iter, status);
     DeviceGuard guard(device);
-    std::vector<FnHost> fh, gh;
-    for (int j = 0; j < k; ++j) {
-      fh.push_back(fn_host(&f[j]));
-      gh.push_back(fn_host(&g[j]));
-    }
-    solve_many(dtype, static_cast<int>(ord), k, m, n, A, mem, device, fh.data(), gh.data(), rho,
+    solve_many(dtype, static_cast<int>(ord), k, m, n, A, mem, device, fg.first.data(), fg.second.data(), rho,
                make_params(1.0, abs_tol, rel_tol, max_iter, verbose, adaptive_rho, gap_stop),
                BatchOut{x, y, l, mu, optval, final_iter, status});
     return 0;

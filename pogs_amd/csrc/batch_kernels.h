@@ -1,6 +1,6 @@
-// Kernels of the batched dense solves (dense_batch.h): multi-vector passes over a stored row-major matrix on the
-// matrix cores, and the per-problem element-wise stages.  Their own translation unit (batch_kernels.hip), so that the
-// per-shape code objects of the solo solver stay as small as they are.
+// Kernels of the batched solves: multi-vector passes over a stored row-major matrix on the matrix cores (dense batch,
+// dense_batch.h), and the element-wise stages and sums of the loop both batches share (batch_admm.h).  Their own
+// translation unit (batch_kernels.hip), so that the per-shape code objects of the solo solver stay small.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,4 +1,4 @@
-// Kernels of the batched dense solves: see batch_kernels.h and dense_batch.h.
+// Kernels of the batched dense solves: see batch_kernels.h, batch_admm.h (the loop) and dense_batch.h (the passes).
 //
 // Determinism: every multi-vector product is a v_mfma_*_16x16x4 chain, which is a k-ordered FMA chain per output
 // element, so the arithmetic of problem j depends neither on the other vectors nor on j's slot; the partials of

@@ -33,16 +33,8 @@ void DenseSolver<T, Tag>::load_problem(const FnHost &f, const FnHost &g, const S
   // scaled copies: h and b shared with the originals (pogs.cpp:608-617)
   launch_scale_objective<T>(f_.view(), fs_.a.p, fs_.c.p, fs_.d.p, fs_.e.p, d_.p, m_, true, s);
   launch_scale_objective<T>(g_.view(), gs_.a.p, gs_.c.p, gs_.d.p, gs_.e.p, e_.p, n_, false, s);
-  ctl_ = AdmmControl<T>();
-  ctl_.abs_tol = static_cast<T>(p.abs_tol);
-  ctl_.rel_tol = static_cast<T>(p.rel_tol);
-  ctl_.max_iter = p.max_iter;
-  ctl_.adaptive_rho = p.adaptive_rho;
-  ctl_.gap_stop = p.gap_stop;
+  ctl_ = make_admm_control<T>(p, p.rho, ctx_.m_global, n_);
   ctl_.say_rho = p.verbose > 3 && ctx_.dist.rank() == 0;
-  ctl_.rho0 = static_cast<T>(p.rho);
-  ctl_.m_glob = ctx_.m_global;
-  ctl_.n = n_;
   loaded_ = true;
   ctx_.sync();  // the host coefficient arrays may be freed by the caller afterwards
 }

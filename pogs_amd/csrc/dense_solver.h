@@ -22,6 +22,7 @@
 #include <limits>
 #include <thread>
 
+#include "batch_admm.h"
 #include "batch_kernels.h"
 #include "cg_kernels.h"
 #include "engine.h"
@@ -214,8 +215,9 @@ class DenseSolver final : public SolverBase {
     ctx_.sync();
   }
 
-  // Batched solves (dense_batch.h): separate buffers; the solo state, a pending warm start and the stats of the last
-  // solo solve stay as they are (except iterations, matvecs and reserved[4..7]).
+  // Batched solves (the loop: batch_admm.h; its passes over the stored matrices: dense_batch.h): separate buffers; the
+  // solo state, a pending warm start and the stats of the last solo solve stay as they are (except iterations, matvecs
+  // and reserved[4..7]).
   void solve_batch(int k, const FnHost *f, const FnHost *g, const double *rho, const SolveParams &p,
                    const BatchOut &out) override;
 

@@ -592,6 +592,23 @@ struct SolveParams {
   bool adaptive_rho, gap_stop;
 };
 
+// The control block of one problem from the caller's parameters, reset and ready to iterate (host side).  rho0: the
+// problem's own initial rho; m_glob: rows of the whole matrix.  say_rho stays off: the solo solvers switch it on.
+template <typename T>
+inline AdmmControl<T> make_admm_control(const SolveParams &p, double rho0, size_t m_glob, size_t n) {
+  AdmmControl<T> c;
+  c.abs_tol = static_cast<T>(p.abs_tol);
+  c.rel_tol = static_cast<T>(p.rel_tol);
+  c.max_iter = p.max_iter;
+  c.adaptive_rho = p.adaptive_rho;
+  c.gap_stop = p.gap_stop;
+  c.rho0 = static_cast<T>(rho0);
+  c.m_glob = m_glob;
+  c.n = n;
+  c.reset();
+  return c;
+}
+
 struct FnHost {  // host SoA, element type = solver dtype
   const void *a, *b, *c, *d, *e;
   const int *h;

@@ -736,19 +736,7 @@ void solve_many_t(int ord, int kk, size_t m_, size_t n_, const void *Ain, int me
     if (!hp.empty()) POGS_HIP_CHECK(hipMemcpyAsync(hpool.p, hp.data(), hp.size() * sizeof(int), hipMemcpyHostToDevice, s));
     POGS_HIP_CHECK(hipMemcpyAsync(fnd.p, fh.data(), 2 * static_cast<size_t>(cnt) * sizeof(ManyFn<T>),
                                   hipMemcpyHostToDevice, s));
-    for (int q = 0; q < cnt; ++q) {
-      AdmmControl<T> &c = ch[q];
-      c = AdmmControl<T>();
-      c.abs_tol = static_cast<T>(p.abs_tol);
-      c.rel_tol = static_cast<T>(p.rel_tol);
-      c.max_iter = p.max_iter;
-      c.adaptive_rho = p.adaptive_rho;
-      c.gap_stop = p.gap_stop;
-      c.rho0 = static_cast<T>(rho0 ? rho0[j0 + q] : 1.0);
-      c.m_glob = m_;
-      c.n = n_;
-      c.reset();
-    }
+    for (int q = 0; q < cnt; ++q) ch[q] = make_admm_control<T>(p, rho0 ? rho0[j0 + q] : 1.0, m_, n_);
     POGS_HIP_CHECK(hipMemcpyAsync(ctld.p, ch.data(), static_cast<size_t>(cnt) * sizeof(AdmmControl<T>),
                                   hipMemcpyHostToDevice, s));
     POGS_HIP_CHECK(hipMemsetAsync(done.p, 0, sizeof(unsigned), s));

@@ -22,6 +22,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "batch_admm.h"
 #include "cg_fused.h"
 #include "cg_kernels.h"
 #include "engine.h"
@@ -626,7 +627,8 @@ class SparseSolver final : public SolverBase {
     ctx_.sync();
   }
 
-  // k problems on the handle's matrix, every product with A / A^T shared (sparse_batch.h)
+  // k problems on the handle's matrix, every product with A / A^T shared (the loop: batch_admm.h; the
+  // products and the batched CGLS: sparse_batch.h)
   void solve_batch_sparse(int kb, const FnHost *f, const FnHost *g, const double *rho0, const SolveParams &p,
                           const BatchOut &out) override;
 
@@ -1282,16 +1284,8 @@ class SparseSolver final : public SolverBase {
     // prox step: 16 of its 44 bytes per element
     uni_f_ = probe_uniform<T>(fview(), m_, s);
     uni_g_ = probe_uniform<T>(gview(), n_, s);
-    ctl_ = AdmmControl<T>();
-    ctl_.abs_tol = static_cast<T>(p.abs_tol);
-    ctl_.rel_tol = static_cast<T>(p.rel_tol);
-    ctl_.max_iter = p.max_iter;
-    ctl_.adaptive_rho = p.adaptive_rho;
-    ctl_.gap_stop = p.gap_stop;
+    ctl_ = make_admm_control<T>(p, p.rho, ctx_.m_global, n_);
     ctl_.say_rho = p.verbose > 3 && ctx_.dist.rank() == 0;
-    ctl_.rho0 = static_cast<T>(p.rho);
-    ctl_.m_glob = ctx_.m_global;
-    ctl_.n = n_;
     loaded_ = true;
     ctx_.sync();
   }

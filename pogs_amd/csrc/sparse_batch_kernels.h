@@ -1,7 +1,7 @@
 // Kernels of the batched sparse solves (sparse_batch.h): a multi-vector CSR product over the handle's equilibrated
 // plain CSR copies (A and A^T), the pack of K operand vectors into one interleaved gather, and the batched CGLS
 // vector stages.  Their own translation unit (sparse_batch_kernels.hip), so that the solo code objects stay as they
-// are.  The element-wise ADMM stages are those of the dense batch (batch_kernels.h).
+// are.  The element-wise ADMM stages are those of the shared loop (batch_admm.h, batch_kernels.h).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,4 +1,4 @@
-// Kernels of the batched sparse solves: see sparse_batch_kernels.h and sparse_batch.h.
+// Kernels of the batched sparse solves: see sparse_batch_kernels.h and sparse_batch.h (the loop: batch_admm.h).
 //
 // Multi-vector CSR product.  A row is owned by L lanes of one wave (L = 16 / 32 / 64 from the matrix's mean row
 // length, about four non-zeros per lane); lane i takes the row's non-zeros i, i + L, i + 2L, ... in order, reads each stored value and index once and
