@@ -421,6 +421,37 @@ int PogsAmdGramCheck(int dtype, int kdim, int k, const void *P, size_t lda, int 
  * error: the square root of the bad pivot is NaN, and NaN spreads from there (the reference's
  * linalg_cholesky_decomp reports an error instead). */
 int PogsAmdCholCheck(int dtype, int n, const void *H, size_t ldh, void *L, void *W, void *U, size_t ldo);
+/* Diagnostic of the solo sparse solver's product.  HOST arrays; invalid arguments are refused before any device work, as
+ * above.  The entry builds what the constructor of a sparse handle builds before its equilibration, by the same
+ * functions: both CSR copies (the second transposed on the device), and of each the tiled lane-stream copy the product
+ * streams, or the row blocks of the plain CSR kernel where that copy is not built.  The matrix (nrows x ncols) is given
+ * as PogsAmdCreateSparse takes it: ord = ROW_MAJ: CSR (ptr: nrows + 1), COL_MAJ: CSC (ptr: ncols + 1); ptr[0] == 0,
+ * indices need not be sorted and entries may repeat (they add up).  A matrix without entries is refused.
+ *   num_cu: the CU count the geometry is chosen for (0: the device's).
+ *   format: 0 as a solve chooses (POGS_AMD_SELL_FORMAT and POGS_AMD_SPMV included), 1 a row tag per element, 2 two id
+ *     slots per batch, 3 the plain CSR kernel on both copies.
+ *   force_rr_rows, force_ncg: 0, or the rows per row range (a multiple of 64 in [512, 16384 fp32 / 6144 fp64]) and the
+ *     number of column groups (1 .. min(column blocks, 32)) that replace the solver's choice on the copy the product
+ *     runs on (A for trans = 'n', A^T for 't'); the other copy is built as a solve builds it.
+ *   scale: after the build every value of both CSR copies is multiplied by it and the tiled values are written a second
+ *     time from the CSR copy, through the table of positions the first fill recorded (what a handle does with the
+ *     equilibrated values); scale = 1 takes the same way.
+ *   Then one product with the functor of the norm estimate:  y = alpha op(A)' x' + beta y,  op = A (trans 'n') or A^T
+ *   ('t'), every entry of A squared when sq != 0, x' = x / sqrt(x_nrm2) (x_nrm2 = 0: x itself, no scalar is read);
+ *   *sumsq = the sum of the squares of the new y, added up in fp64 by the launches a solve uses.
+ *   x: xlen >= (columns of op) elements, all uploaded; y: ylen >= (rows of op) elements, uploaded before and downloaded
+ *   after, so that what lies behind the vectors must come back as it was.
+ *   info (16 ints), 8 for A and 8 for A^T: {1 if tiled, 1 if two id slots, rows per row range, row ranges, column
+ *     blocks, column groups, stored 64-element units, why not tiled}; the last is 0 on a tiled copy, else 1 no
+ *     non-zeros (a handle's code; this entry refuses such a matrix), 2 the plan (6 to 10 bytes per (row, column block)) too large, 3 a stream offset of the planner out of
+ *     range, 4 padding beyond 4 nnz + 2^22 stored elements, 5 a row holds more than 65535 entries in one column block
+ *     (repeated entries), 6 the plain kernel pinned.  The geometry fields are 0 on a copy that is not tiled.
+ *   t_ptr, t_ind, t_val (each may be NULL): the CSR copy built on the device (A^T for CSR input, A for CSC input) as
+ *     the build leaves it, before `scale`: rows sorted by index, equal indices by the value's bit pattern as unsigned. */
+int PogsAmdSpmvCheck(int dtype, enum ORD ord, int nrows, int ncols, const int *ptr, const int *ind, const void *val,
+                     int num_cu, int format, int force_rr_rows, int force_ncg, double scale, char trans, int sq,
+                     double x_nrm2, double alpha, double beta, const void *x, size_t xlen, void *y, size_t ylen,
+                     double *sumsq, int *info, int *t_ptr, int *t_ind, void *t_val);
 /* W = L^-1 and U = W^T of a dense handle with the direct projector, L L^T = I + A_eq^T A_eq (m > n) or
  * I + A_eq A_eq^T: HOST outputs of k x k, k = min(m, n), either may be NULL.  On row shards every rank holds the
  * factor of the whole matrix.  POGS_ERROR on a sparse handle and on one that runs the CGLS projector. */

@@ -164,9 +164,17 @@ lib.PogsAmdManySetupCheck.argtypes = [c_int, c_int, c_int, c_size_t, c_size_t, c
                                       c_void_p, c_void_p, c_void_p]
 lib.PogsAmdGramCheck.argtypes = [c_int, c_int, c_int, c_void_p, c_size_t, c_int, c_int, c_void_p, c_size_t, c_void_p]
 lib.PogsAmdCholCheck.argtypes = [c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_size_t]
+lib.PogsAmdSpmvCheck.argtypes = [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                 c_double, c_char, c_int, c_double, c_double, c_double, c_void_p, c_size_t, c_void_p,
+                                 c_size_t, ctypes.POINTER(c_double), c_void_p, c_void_p, c_void_p, c_void_p]
 lib.PogsAmdGetFactor.argtypes = [c_void_p, c_void_p, c_void_p]
 GRAM_AUTO, GRAM_NATIVE, GRAM_TILE_128, GRAM_TILE_256 = 0, 1, 128, 256   # `force` of PogsAmdGramCheck
 GRAM_INFO = ("path", "tile", "ksplit", "kchunk", "kacc", "units", "unit_rows", "tile_map")
+SPMV_AUTO, SPMV_TAGS, SPMV_TWO, SPMV_PLAIN = 0, 1, 2, 3   # `format` of PogsAmdSpmvCheck
+SPMV_INFO = ("tiled", "two", "rr_rows", "nrr", "ncb", "ncg", "units", "why")
+# `why` of a copy that is not tiled
+SPMV_WHY = {0: "tiled", 1: "no non-zeros", 2: "plan too large", 3: "planner range", 4: "padding", 5: "row count over 16 bits",
+            6: "pinned plain"}
 
 
 class PogsAmdPoolInfo(ctypes.Structure):
@@ -203,7 +211,8 @@ ABI_SYMBOLS = [
     "PogsAmdPoolStats", "PogsAmdPoolTrim",
     "PogsAmdProxEval", "PogsAmdFuncEval", "PogsAmdProjSubgradEval", "PogsAmdGetEquil", "PogsAmdProject", "PogsAmdMul", "PogsAmdRandUniform",
     "PogsAmdReadBandwidth", "PogsAmdWaveSumCheck", "PogsAmdBatchRowsCheck", "PogsAmdBatchColsCheck",
-    "PogsAmdSpBatchSpmvCheck", "PogsAmdManySetupCheck", "PogsAmdGramCheck", "PogsAmdCholCheck", "PogsAmdGetFactor",
+    "PogsAmdSpBatchSpmvCheck", "PogsAmdManySetupCheck", "PogsAmdGramCheck", "PogsAmdCholCheck",
+    "PogsAmdSpmvCheck", "PogsAmdGetFactor",
 ]
 
 
@@ -348,6 +357,41 @@ def gram_check(P, k, G, force=GRAM_AUTO, num_cu=0):
                             info.ctypes.data) != 0:
         raise RuntimeError(last_error())
     return G, dict(zip(GRAM_INFO, (int(v) for v in info)))
+
+
+def spmv_check(ptr, ind, val, shape, x, y, trans="n", ord=ROW_MAJ, num_cu=0, format=SPMV_AUTO, force_rr_rows=0,
+               force_ncg=0, scale=1.0, sq=False, x_nrm2=0.0, alpha=1.0, beta=0.0, transpose=False):
+    """(y, sumsq, (info_A, info_At)[, (t_ptr, t_ind, t_val)]): y = alpha op(A) x + beta y by the solo sparse solver's
+    product on copies built as a sparse handle builds them (include/pogs_amd.h: PogsAmdSpmvCheck).  shape = (nrows,
+    ncols) of A; ptr / ind / val: its CSR (ord = ROW_MAJ) or CSC (COL_MAJ) arrays.  x and y may be longer than the
+    vectors: the whole of x is uploaded, the whole of y uploaded and downloaded.  info_*: dicts of SPMV_INFO.
+    transpose=True also returns the CSR copy built on the device.  Returns a new array; y itself is not changed."""
+    import numpy as np
+    ptr, ind = np.ascontiguousarray(ptr, dtype=np.int32), np.ascontiguousarray(ind, dtype=np.int32)
+    val, x = np.ascontiguousarray(val), np.ascontiguousarray(x)
+    y = np.array(y, order="C", copy=True)
+    code = _dtype_code(val, x, y)
+    nrows, ncols = int(shape[0]), int(shape[1])
+    r1, c1 = (nrows, ncols) if ord == ROW_MAJ else (ncols, nrows)
+    if ptr.ndim != 1 or ptr.size != r1 + 1 or x.ndim != 1 or y.ndim != 1:
+        raise ValueError("ptr (rows of the given copy + 1), x and y vectors")
+    nnz = max(int(ptr[-1]), 0)
+    if ind.size < nnz or val.size < nnz:
+        raise ValueError("ind and val must hold ptr[-1] entries")
+    info = np.zeros(16, dtype=np.int32)
+    sumsq = c_double(0.0)
+    t = None
+    if transpose:
+        t = (np.zeros(c1 + 1, np.int32), np.zeros(max(nnz, 1), np.int32), np.zeros(max(nnz, 1), val.dtype))
+    if lib.PogsAmdSpmvCheck(code, ord, nrows, ncols, ptr.ctypes.data, ind.ctypes.data, val.ctypes.data, num_cu, format,
+                            force_rr_rows, force_ncg, scale, trans.encode(), int(bool(sq)), x_nrm2, alpha, beta,
+                            x.ctypes.data, x.size, y.ctypes.data, y.size, ctypes.byref(sumsq), info.ctypes.data,
+                            *((None, None, None) if t is None else (a.ctypes.data for a in t))) != 0:
+        raise RuntimeError(last_error())
+    infos = tuple(dict(zip(SPMV_INFO, (int(v) for v in info[8 * c:8 * c + 8]))) for c in range(2))
+    if t is None:
+        return y, sumsq.value, infos
+    return y, sumsq.value, infos, (t[0], t[1][:nnz], t[2][:nnz])
 
 
 def chol_check(H, ldo=None):

@@ -9,6 +9,7 @@
 #include "factor_check.h"
 #include "many_kernels.h"
 #include "sparse_batch_kernels.h"
+#include "spmv_check.h"
 #include "prox.h"
 #include "stream.h"
 #include "vec_kernels.h"
@@ -660,6 +661,19 @@ int PogsAmdCholCheck(int dtype, int n, const void *H, size_t ldh, void *L, void 
     else
       chol_check<double>(n, static_cast<const double *>(H), ldh, static_cast<double *>(L), static_cast<double *>(W),
                          static_cast<double *>(U), ldo);
+    return 0;
+  });
+}
+
+int PogsAmdSpmvCheck(int dtype, enum ORD ord, int nrows, int ncols, const int *ptr, const int *ind, const void *val,
+                     int num_cu, int format, int force_rr_rows, int force_ncg, double scale, char trans, int sq,
+                     double x_nrm2, double alpha, double beta, const void *x, size_t xlen, void *y, size_t ylen,
+                     double *sumsq, int *info, int *t_ptr, int *t_ind, void *t_val) {
+  return guarded([&]() {
+    const SpmvCheckArgs a{dtype, static_cast<int>(ord), nrows, ncols, ptr, ind, val, num_cu, format, force_rr_rows,
+                          force_ncg, scale, trans, sq, x_nrm2, alpha, beta, x, xlen, y, ylen, sumsq, info, t_ptr, t_ind,
+                          t_val};
+    spmv_check(a);
     return 0;
   });
 }

@@ -474,7 +474,7 @@ __global__ void __launch_bounds__(kSellTpb) spmv_sell_kernel(SellView<T> A, cons
 
 // ---------------------------------------------------------------------------------------------
 // Build (device).  Temporaries per (tile, local row): cnt (non-zeros, uint16: a tile is at most
-// 24576 wide), soff (stream << 23 | offset of the row inside its stream).
+// 18432 wide), soff (stream << 23 | offset of the row inside its stream).
 // ---------------------------------------------------------------------------------------------
 struct SellDims {
   int nrows, ncols, rr_rows, nrr, ncb, bw;
@@ -484,7 +484,22 @@ struct SellDims {
 // row whose column blocks do not decrease the first element of every run of equal blocks walks forward to the run's end and
 // writes its length; any other row is counted by one lane, element by element (as every row was, one thread per row, until
 // round 5: 2.3 ms per copy at C4).
-__global__ void __launch_bounds__(256) sell_count_kernel(const int *ind, const int *ptr, SellDims D, unsigned short *cnt) {
+//
+// The counts are 16 bits wide.  A tile is at most SellCfg<T>::BW = 18432 (fp32) or 12288 (fp64) columns wide, so a row
+// of DISTINCT columns always fits, but the
+// interface takes repeated entries (the product adds them up) and a row that names a few columns 70 000 times does not:
+// stored as `count mod 65536` it would be planned as a short row and filled as a long one, across the tiles behind it
+// and the end of the arrays.  Such a count is stored as 65535 and *err |= 16: the caller keeps the plain CSR kernel for
+// that copy, as for a padding blow-up (nothing is filled from a plan that carries the bit).
+constexpr int kSellCntMax = 0xFFFF;
+constexpr int kSellErrCount = 16;
+// why a copy has no tiled form and runs the plain CSR kernel (DevCsr::sell_why, reported by PogsAmdSpmvCheck): no
+// non-zeros; the plan too large to index; an *err bit of sell_plan_kernel (a stream offset out of range, a stream's
+// row count); padding beyond 4 nnz + 2^22 stored elements; kSellErrCount; the plain kernel pinned by the caller
+constexpr int kSellWhyNone = 0, kSellWhyEmpty = 1, kSellWhyPlan = 2, kSellWhyRange = 3, kSellWhyPadding = 4,
+              kSellWhyCount = 5, kSellWhyPinned = 6;
+__global__ void __launch_bounds__(256) sell_count_kernel(const int *ind, const int *ptr, SellDims D, unsigned short *cnt,
+                                                         int *err) {
   const int lane = threadIdx.x & 63;
   const int w = static_cast<int>((blockIdx.x * blockDim.x + threadIdx.x) >> 6), nw = static_cast<int>((gridDim.x * blockDim.x) >> 6);
   for (int r = w; r < D.nrows; r += nw) {
@@ -499,12 +514,15 @@ __global__ void __launch_bounds__(256) sell_count_kernel(const int *ind, const i
         if (k > p0 && ind[k - 1] / D.bw == cb) continue;   // not the first of its run
         int e = k + 1;
         while (e < p1 && ind[e] / D.bw == cb) ++e;
-        cnt[(static_cast<size_t>(rr) * D.ncb + cb) * D.rr_rows + lr] = static_cast<unsigned short>(e - k);
+        if (e - k > kSellCntMax) atomicOr(err, kSellErrCount);
+        cnt[(static_cast<size_t>(rr) * D.ncb + cb) * D.rr_rows + lr] = static_cast<unsigned short>(min(e - k, kSellCntMax));
       }
     } else if (lane == 0) {
       for (int k = p0; k < p1; ++k) {
         const int cb = ind[k] / D.bw;
-        cnt[(static_cast<size_t>(rr) * D.ncb + cb) * D.rr_rows + lr] += 1;
+        unsigned short &c = cnt[(static_cast<size_t>(rr) * D.ncb + cb) * D.rr_rows + lr];
+        if (c == kSellCntMax) atomicOr(err, kSellErrCount);
+        else c += 1;
       }
     }
   }

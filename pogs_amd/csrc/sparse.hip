@@ -29,6 +29,7 @@
 #include "reduce.h"
 #include "sell.h"
 #include "sparse_batch_kernels.h"
+#include "spmv_check.h"
 #include "vec_kernels.h"
 
 namespace pogs_amd {
@@ -518,6 +519,7 @@ struct DevCsr {
   DevBuf<unsigned> ssoff;
   DevBuf<unsigned> sdst;         // position of every CSR element in the tiled copy, kept from the first fill to the refill
   bool sell_ready = false;
+  int sell_why = kSellWhyNone;   // why the plain kernel runs instead (sell.h: kSellWhy*), kSellWhyNone on a tiled copy
   int rr_rows = 0, nrr = 0, ncb = 0, ncg = 1;
   int two = 0;                   // storage format (SellView::two)
   size_t sell_elems = 0;
@@ -579,6 +581,28 @@ class SparseSolver final : public SolverBase {
     norm_est();
     ctx_.sync();
     ctx_.stats.t_init_s = wall_s() - t0;
+  }
+
+  // PogsAmdSpmvCheck: the constructor above up to and excluding equilibrate(), with the switches a solve reads from
+  // the environment (and the two geometry choices of build_sell) as arguments; see spmv_check() below
+  SparseSolver(const SpmvCheckArgs &a, int m, int n) {
+    ctx_.init(-1, 0);
+    if (a.num_cu > 0) ctx_.num_cu = a.num_cu;
+    m_ = m;
+    n_ = n;
+    ctx_.m_global = static_cast<size_t>(m);
+    const int r1 = (a.ord == ROW_MAJ) ? m : n;
+    nnz_ = static_cast<size_t>(a.ptr[r1]);
+    chk_format_ = a.format;
+    chk_rr_ = a.force_rr_rows;
+    chk_ncg_ = a.force_ncg;
+    chk_copy_ = (a.trans == 'n') ? 0 : 1;
+    build_structure(a.ord, a.val, a.ptr, a.ind, POGS_AMD_HOST);
+    spmv_grid_ = ctx_.num_cu * 8;
+    size_t sg = static_cast<size_t>(spmv_grid_);   // as alloc_state: the workgroups that write scalar partials in one launch
+    if (A_.sell_ready) sg = std::max(sg, static_cast<size_t>(A_.nrr) * A_.ncg);
+    if (At_.sell_ready) sg = std::max(sg, static_cast<size_t>(At_.nrr) * At_.ncg);
+    ctx_.ensure_spart(sg * 4 + 64);
   }
 
   ~SparseSolver() override { begin_destroy(ctx_); }
@@ -680,6 +704,58 @@ class SparseSolver final : public SolverBase {
     ctx_.sync();
   }
 
+  // PogsAmdSpmvCheck on a handle built by the structure-only constructor: the second write of the values (scale_csr_kernel
+  // and refill_sell, as equilibrate() ends), then one product with the functor of the norm estimate
+  void spmv_check(const SpmvCheckArgs &a) {
+    hipStream_t s = ctx_.stream;
+    const DevCsr<T> &built = first_is_A_ ? At_ : A_;   // the copy build_structure transposed on the device
+    if (a.t_ptr) POGS_HIP_CHECK(hipMemcpyAsync(a.t_ptr, built.ptr.p, (built.nrows + 1) * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (a.t_ind && nnz_) POGS_HIP_CHECK(hipMemcpyAsync(a.t_ind, built.ind.p, nnz_ * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (a.t_val && nnz_) POGS_HIP_CHECK(hipMemcpyAsync(a.t_val, built.val.p, nnz_ * sizeof(T), hipMemcpyDeviceToHost, s));
+    {
+      const size_t mx = static_cast<size_t>(std::max(m_, n_));
+      DevBuf<T> sc(mx), one(mx);
+      launch_fill<T>(sc.p, static_cast<T>(a.scale), mx, s);
+      launch_fill<T>(one.p, static_cast<T>(1), mx, s);
+      const int g = ctx_.num_cu * 8;   // (spart holds 4 g + 64 partials: the constructor)
+      hipLaunchKernelGGL(scale_csr_kernel<T>, dim3(g), dim3(256), 0, s, A_.val.p, A_.ind.p, A_.ptr.p, m_, sc.p, one.p, ctx_.spart.p);
+      hipLaunchKernelGGL(scale_csr_kernel<T>, dim3(g), dim3(256), 0, s, At_.val.p, At_.ind.p, At_.ptr.p, n_, sc.p, one.p,
+                         ctx_.spart.p + g);
+      refill_sell(A_);
+      refill_sell(At_);
+      ctx_.sync();   // sc / one are freed at scope exit
+    }
+    const bool tr = a.trans == 't';
+    const DevCsr<T> &M = tr ? At_ : A_;
+    DevBuf<T> vin(a.xlen), vout(a.ylen);
+    POGS_HIP_CHECK(hipMemcpyAsync(vin.p, a.x, a.xlen * sizeof(T), hipMemcpyHostToDevice, s));
+    POGS_HIP_CHECK(hipMemcpyAsync(vout.p, a.y, a.ylen * sizeof(T), hipMemcpyHostToDevice, s));
+    const double *x_nrm2 = nullptr;
+    if (a.x_nrm2 != 0.0) {
+      POGS_HIP_CHECK(hipMemcpyAsync(ctx_.S.p + kPowX2, &a.x_nrm2, sizeof(double), hipMemcpyHostToDevice, s));
+      x_nrm2 = ctx_.S.p + kPowX2;
+    }
+    const SpAxpbyNormOp<T> op{static_cast<T>(a.alpha), static_cast<T>(a.beta), vout.p, vout.p};
+    if (a.sq) spmv<true>(M, vin.p, x_nrm2, op, ctx_.S.p + kPowSx2, 0);
+    else spmv<false>(M, vin.p, x_nrm2, op, ctx_.S.p + kPowSx2, 0);
+    POGS_HIP_CHECK(hipGetLastError());
+    POGS_HIP_CHECK(hipMemcpyAsync(a.y, vout.p, a.ylen * sizeof(T), hipMemcpyDeviceToHost, s));
+    POGS_HIP_CHECK(hipMemcpyAsync(a.sumsq, ctx_.S.p + kPowSx2, sizeof(double), hipMemcpyDeviceToHost, s));
+    ctx_.sync();
+    for (int c = 0; c < 2; ++c) {
+      const DevCsr<T> &C = c ? At_ : A_;
+      int *o = a.info + 8 * c;
+      o[0] = C.sell_ready ? 1 : 0;
+      o[1] = C.sell_ready ? C.two : 0;
+      o[2] = C.sell_ready ? C.rr_rows : 0;
+      o[3] = C.sell_ready ? C.nrr : 0;
+      o[4] = C.sell_ready ? C.ncb : 0;
+      o[5] = C.sell_ready ? C.ncg : 0;
+      o[6] = static_cast<int>(C.sell_elems / 64);
+      o[7] = C.sell_why;
+    }
+  }
+
   void mul(char trans, double alpha, const void *x, double beta, void *y) override {
     hipStream_t s = ctx_.stream;
     const bool tr = (trans == 't' || trans == 'T');
@@ -741,9 +817,13 @@ class SparseSolver final : public SolverBase {
     first.ncols = c1;
     second.ncols = r1;
     const char *ev = std::getenv("POGS_AMD_SPMV");
-    if (!(ev && ev[0] == 'p')) {   // POGS_AMD_SPMV=plain keeps the plain CSR kernel (testing aid)
-      build_sell(first);
-      build_sell(second);
+    const bool plain = chk_format_ == kSpmvFormatPlain || (chk_format_ == kSpmvFormatAuto && ev && ev[0] == 'p');
+    if (!plain) {   // POGS_AMD_SPMV=plain keeps the plain CSR kernel (testing aid)
+      const int first_copy = (ord == ROW_MAJ) ? 0 : 1;   // 0: A, 1: A^T
+      build_sell(first, chk_copy_ == first_copy);
+      build_sell(second, chk_copy_ == 1 - first_copy);
+    } else {
+      first.sell_why = second.sell_why = kSellWhyPinned;
     }
     // row blocks of the plain CSR kernel: only for a copy that did not get its tiled form (the host
     // walk over every row and the copy of the transposed ptr array cost ~5 ms at C4)
@@ -783,9 +863,11 @@ class SparseSolver final : public SolverBase {
   // Tiled lane-stream copy of M (sell.h): structure and values now, values again after the
   // equilibration has rescaled the CSR copy (refill_sell).  Skipped (the plain CSR kernel then
   // runs) when the bookkeeping could not be indexed with 32 bits or the padding would blow up.
-  void build_sell(DevCsr<T> &M) {
+  // forced (PogsAmdSpmvCheck only): chk_rr_ / chk_ncg_, where not 0, replace the two choices made below
+  void build_sell(DevCsr<T> &M, bool forced = false) {
     hipStream_t s = ctx_.stream;
     constexpr int BW = SellCfg<T>::BW, RRMAX = SellCfg<T>::RR;
+    M.sell_why = kSellWhyEmpty;
     if (M.nnz == 0) return;
     const int ncb = (M.ncols + BW - 1) / BW;
     // rows per row range: as many as the LDS holds, fewer when the matrix would otherwise give
@@ -841,16 +923,21 @@ class SparseSolver final : public SolverBase {
           if (c < best_c * (1 - 1e-3)) { best_c = c; rr_rows = rr; ncg = g; }
         }
     }
+    if (forced && chk_rr_) rr_rows = chk_rr_;
+    if (forced && chk_ncg_) ncg = chk_ncg_;
     const int nrr = (M.nrows + rr_rows - 1) / rr_rows;
     const long long ntiles = static_cast<long long>(nrr) * ncb;
     const long long nq = ntiles * rr_rows;
+    M.sell_why = kSellWhyPlan;
     if (ntiles >= (1LL << 30) || nq >= (1LL << 31)) return;
     // storage format: the planner lays the tile out both ways and the smaller matrix is kept (7 bytes per stored
     // fp32 element with two id slots per batch, 8 with a tag per element -- but the first needs padding when most
     // rows of a tile hold a single element).  POGS_AMD_SELL_FORMAT=tags / two pins it (tests, A/B measurements).
     static_assert(SellCfg<T>::BW <= 32768, "bit 15 of a local column is the row-end flag of the two-slot format");
     int want_two = -1;
-    if (const char *f = std::getenv("POGS_AMD_SELL_FORMAT")) want_two = std::strcmp(f, "two") == 0 ? 1 : (std::strcmp(f, "tags") == 0 ? 0 : -1);
+    if (chk_format_ == kSpmvFormatTags) want_two = 0;
+    else if (chk_format_ == kSpmvFormatTwo) want_two = 1;
+    else if (const char *f = std::getenv("POGS_AMD_SELL_FORMAT")) want_two = std::strcmp(f, "two") == 0 ? 1 : (std::strcmp(f, "tags") == 0 ? 0 : -1);
     {
       // The plan keeps 6 bytes per (row, column block) pair (count, stream offset) and 4 more (the second layout's
       // offsets) unless the tag format is pinned -- on a matrix with many column blocks and few non-zeros per row
@@ -868,12 +955,12 @@ class SparseSolver final : public SolverBase {
     M.scnt.alloc(nq); M.ssoff.alloc(nq);
     if (want_two != 0) soff2.alloc(nq);
     M.scnt.zero(s);
-    const int g = std::max(1, std::min((M.nrows + 3) / 4, ctx_.num_cu * 32));   // a wavefront per row, four per workgroup
-    hipLaunchKernelGGL(sell_count_kernel, dim3(g), dim3(256), 0, s, M.ind.p, M.ptr.p, D, M.scnt.p);
     DevBuf<int> nu(ntiles + 1), nu2, err(1);
+    err.zero(s);
+    const int g = std::max(1, std::min((M.nrows + 3) / 4, ctx_.num_cu * 32));   // a wavefront per row, four per workgroup
+    hipLaunchKernelGGL(sell_count_kernel, dim3(g), dim3(256), 0, s, M.ind.p, M.ptr.p, D, M.scnt.p, err.p);
     DevBuf<int> tile_unit2;
     if (soff2.p) { nu2.alloc(ntiles + 1); tile_unit2.alloc(ntiles + 1); }
-    err.zero(s);
     M.tile_unit.alloc(ntiles + 1);
     const int gt = static_cast<int>(std::min<long long>(ntiles, ctx_.num_cu * 8));
     {
@@ -911,10 +998,14 @@ class SparseSolver final : public SolverBase {
                    static_cast<double>(tot) * 64.0 / static_cast<double>(M.nnz));
     // (a padding blow-up beyond 4x the non-zeros -- a few very long rows among many short ones in
     // a tile -- is left to the plain kernel)
+    // (bit 16, sell_count_kernel: a row holds more non-zeros in one tile than the 16-bit counts of the plan can say --
+    // only an input that repeats entries gets there -- and the plan made from the clipped counts must not be filled)
     if (herr != 0 || tot <= 0 || static_cast<size_t>(tot) * 64 > 4 * M.nnz + (static_cast<size_t>(1) << 22)) {
+      M.sell_why = (herr & kSellErrCount) ? kSellWhyCount : (herr != 0 ? kSellWhyRange : kSellWhyPadding);
       M.scnt.release(); M.ssoff.release(); M.tile_unit.release();
       return;
     }
+    M.sell_why = kSellWhyNone;
     M.sell_elems = static_cast<size_t>(tot) * 64;
     M.sval.alloc(M.sell_elems);
     M.sloc.alloc(M.sell_elems);
@@ -1688,6 +1779,9 @@ class SparseSolver final : public SolverBase {
   size_t nnz_ = 0;
   bool first_is_A_ = true;
   bool multi_ = false;
+  // PogsAmdSpmvCheck (all 0 / -1 in a solve): storage format pinned by argument, and the row-range height and group
+  // count that replace build_sell's on copy chk_copy_ (0: A, 1: A^T)
+  int chk_format_ = kSpmvFormatAuto, chk_rr_ = 0, chk_ncg_ = 0, chk_copy_ = -1;
   DevBuf<T> tsum_;   // row shards: this rank's A^T partial sums before the all-reduce
   DevBuf<T> cg_u_;   // row shards, device-resident CG loop: A^T r over all ranks, kept by recurrence
   int spmv_grid_ = 2048;
@@ -1728,6 +1822,39 @@ SolverBase *make_sparse_solver(int dtype, int ord, size_t m, size_t n, size_t nn
   if (dtype == POGS_AMD_F32) return new SparseSolver<float>(ord, m, n, nnz, data, ptr, ind, mem, opt, dist);
   if (dtype == POGS_AMD_F64) return new SparseSolver<double>(ord, m, n, nnz, data, ptr, ind, mem, opt, dist);
   throw Error("unknown dtype");
+}
+
+namespace {
+template <typename T>
+void spmv_check_t(const SpmvCheckArgs &a, int m, int n) {
+  SparseSolver<T> s(a, m, n);
+  s.spmv_check(a);
+}
+}  // namespace
+
+void spmv_check(const SpmvCheckArgs &a) {
+  // every refusal comes before the first HIP call
+  POGS_CHECK(a.dtype == POGS_AMD_F32 || a.dtype == POGS_AMD_F64, "unknown dtype");
+  POGS_CHECK(a.ord == ROW_MAJ || a.ord == COL_MAJ, "unknown ord (ROW_MAJ: CSR, COL_MAJ: CSC)");
+  POGS_CHECK(a.ptr && a.ind && a.val && a.x && a.y && a.sumsq && a.info, "null argument");
+  POGS_CHECK(a.nrows >= 1 && a.ncols >= 1, "nrows and ncols must be >= 1");
+  POGS_CHECK(a.trans == 'n' || a.trans == 't', "trans must be 'n' or 't'");
+  POGS_CHECK(a.num_cu >= 0, "num_cu must be >= 0");
+  POGS_CHECK(a.format >= kSpmvFormatAuto && a.format <= kSpmvFormatPlain,
+             "unknown format (0 as a solve chooses, 1 tags, 2 two id slots, 3 plain CSR kernel)");
+  const int r1 = (a.ord == ROW_MAJ) ? a.nrows : a.ncols;
+  POGS_CHECK(a.ptr[0] == 0, "ptr[0] must be 0");
+  POGS_CHECK(a.ptr[r1] >= 1, "ptr must end at the number of non-zeros (>= 1: an empty matrix has no product to check)");
+  const bool f32 = a.dtype == POGS_AMD_F32;
+  const int nin = a.trans == 'n' ? a.ncols : a.nrows, nout = a.trans == 'n' ? a.nrows : a.ncols;
+  const int bw = f32 ? SellCfg<float>::BW : SellCfg<double>::BW, rrmax = f32 ? SellCfg<float>::RR : SellCfg<double>::RR;
+  POGS_CHECK(a.force_rr_rows == 0 || (a.force_rr_rows % 64 == 0 && a.force_rr_rows >= 512 && a.force_rr_rows <= rrmax),
+             "force_rr_rows must be 0 or a multiple of 64 in [512, the LDS-limit height of the type]");
+  POGS_CHECK(a.force_ncg == 0 || (a.force_ncg >= 1 && a.force_ncg <= std::min((nin + bw - 1) / bw, 32)),
+             "force_ncg must be 0 or in [1, min(column blocks of the copy the product runs on, 32)]");
+  POGS_CHECK(a.xlen >= static_cast<size_t>(nin) && a.ylen >= static_cast<size_t>(nout), "xlen / ylen shorter than the vectors");
+  if (f32) spmv_check_t<float>(a, a.nrows, a.ncols);
+  else spmv_check_t<double>(a, a.nrows, a.ncols);
 }
 
 }  // namespace pogs_amd

@@ -1,0 +1,33 @@
+#pragma once
+// PogsAmdSpmvCheck (include/pogs_amd.h, Part 3): one product of the solo sparse solver on HOST arrays, on copies built
+// by SparseSolver's own build_structure / build_sell / refill_sell (sparse.hip), without the equilibration.
+#include <cstddef>
+
+namespace pogs_amd {
+
+// `format`: the switches a solve reads from POGS_AMD_SELL_FORMAT / POGS_AMD_SPMV, as an argument
+// (info[7], why a copy runs the plain CSR kernel: the kSellWhy* codes of sell.h)
+constexpr int kSpmvFormatAuto = 0, kSpmvFormatTags = 1, kSpmvFormatTwo = 2, kSpmvFormatPlain = 3;
+
+struct SpmvCheckArgs {
+  int dtype, ord, nrows, ncols;
+  const int *ptr, *ind;
+  const void *val;
+  int num_cu, format, force_rr_rows, force_ncg;
+  double scale;
+  char trans;
+  int sq;
+  double x_nrm2, alpha, beta;
+  const void *x;
+  size_t xlen;
+  void *y;
+  size_t ylen;
+  double *sumsq;
+  int *info;
+  int *t_ptr, *t_ind;
+  void *t_val;
+};
+
+void spmv_check(const SpmvCheckArgs &a);
+
+}  // namespace pogs_amd
