@@ -274,6 +274,54 @@ int PogsAmdSolveManyFn(int dtype, enum ORD ord, int k, size_t m, size_t n, const
                        int adaptive_rho, int gap_stop, void *x, void *y, void *l, void *mu,
                        double *optval, unsigned int *final_iter, int *status);
 
+/* A persistent many-problem handle: the k problems of PogsAmdSolveManyFn set up ONCE and re-solved with new f, g.
+ * PogsAmdManyCreate: arguments, envelope and refusals of PogsAmdSolveManyFn (dtype, ord, k >= 1, the two dimension
+ *    caps, CGLS refused).  It runs the one-shot call's setup and keeps resident, for all k problems, the equilibrated
+ *    A_j, d, e, the norm estimate, W_j = L_j^-1, the work vectors and each problem's last un-scaled x and l.  A host A
+ *    is uploaded in chunks whose staging stays under POGS_AMD_MANY_WORKSPACE_MB; a device A is read during create,
+ *    never written and never referenced afterwards.  There is no chunked handle: if the resident footprint cannot be
+ *    allocated, create returns POGS_ERROR, *out is NULL and nothing is left allocated (PogsAmdSolveManyFn remains).
+ * PogsAmdManySolveFn: f, g, tolerances, outputs (layout, NULL-able y, l, mu, optval) and per-problem status as in
+ *    PogsAmdSolveManyFn.  rho_final: NULL or k doubles, each problem's rho when it stopped.  Every call states its
+ *    start (the warm start is not sticky):
+ *    POGS_AMD_MANY_COLD        z = zt = 0; rho NULL = 1.0 each.  A problem's bytes are those PogsAmdSolveManyFn
+ *                              returns for it, however many solves preceded.
+ *    POGS_AMD_MANY_WARM_GIVEN  x0 (k*n) and l0 (k*m), HOST arrays of the handle's dtype, both required.  Per problem
+ *                              the reference's SetInitX + SetInitLambda (src/cpu/pogs.cpp:144-156): x = x0 / e,
+ *                              y = A x, t = l0 / d, xt = (-A^T t) (-1 / rho), yt = t (-1 / rho) with this call's rho
+ *                              of the problem; rho NULL = 1.0 each.
+ *    POGS_AMD_MANY_WARM_LAST   the same initialisation from each problem's own last x, l kept on the device (nothing
+ *                              is uploaded); rho NULL = each problem's last final rho.  Refused before the handle's
+ *                              first solve.  A problem whose last status was neither POGS_SUCCESS nor POGS_MAX_ITER
+ *                              starts cold at rho = 1.
+ *    (WARM_GIVEN uploads x0, l0 into the kept buffers and then takes the WARM_LAST path.)
+ *    verbose > 0 prints the one-line summary of PogsAmdSolveManyFn with the start mode.
+ *    Returns 0 when the problems ran, POGS_ERROR when refused (PogsAmdLastError says why): a NULL handle, f, g, x,
+ *    final_iter or status, an unknown start, and the cases above.  A refused call writes no output and leaves the
+ *    handle as it was.
+ * PogsAmdManyGetInfo: the handle's shape, its resident bytes, create's setup time and the last solve's counters. */
+typedef struct PogsAmdMany PogsAmdMany; /* opaque */
+enum POGS_AMD_MANY_START { POGS_AMD_MANY_COLD = 0, POGS_AMD_MANY_WARM_GIVEN = 1, POGS_AMD_MANY_WARM_LAST = 2 };
+typedef struct PogsAmdManyInfo {
+  int k, dtype;
+  size_t m, n;
+  size_t resident_bytes;              /* device memory the handle holds                      */
+  double setup_s;                     /* PogsAmdManyCreate: upload and setup, wall clock     */
+  /* last PogsAmdManySolveFn */
+  double loop_s;                      /* begin and loop launches, wall clock                 */
+  unsigned long long launches;        /* kernel launches                                     */
+  unsigned long long problem_iters;   /* sum over the problems of the iterations executed    */
+  double reserved[8];
+} PogsAmdManyInfo;
+int PogsAmdManyCreate(PogsAmdMany **out, int dtype, enum ORD ord, int k, size_t m, size_t n, const void *A, int mem,
+                      const PogsAmdOptions *opt);
+int PogsAmdManySolveFn(PogsAmdMany *h, const PogsAmdFn *f, const PogsAmdFn *g, const double *rho, int start,
+                       const void *x0, const void *l0, double abs_tol, double rel_tol, unsigned int max_iter,
+                       unsigned int verbose, int adaptive_rho, int gap_stop, void *x, void *y, void *l, void *mu,
+                       double *optval, unsigned int *final_iter, int *status, double *rho_final);
+int PogsAmdManyGetInfo(const PogsAmdMany *h, PogsAmdManyInfo *out);
+void PogsAmdManyDestroy(PogsAmdMany *h);
+
 /* Benchmark stepping.  PogsAmdBeginRun loads f/g and the solve parameters and
  * resets the ADMM state to the cold start; PogsAmdIterate then advances exactly
  * `iters` ADMM iterations of real solves (restarting from the cold start each

@@ -8,6 +8,7 @@ from .graph import (  # noqa: F401
     Function,
     FunctionObj,
     FunctionVector,
+    ManySolver,
     Ordering,
     Solver,
     _solve_graph_form,
@@ -34,4 +35,5 @@ __version__ = "0.1.0"
 __all__ = [
     "solve_lasso", "solve_ridge", "solve_elastic_net", "solve_logistic", "solve_svm", "solve_huber",
     "solve_nonneg_ls", "solve_lasso_path", "solve_logistic_path", "solve_many", "pogs_solve", "Function", "FunctionObj", "FunctionVector", "Ordering", "Solver",
+    "ManySolver",
 ]

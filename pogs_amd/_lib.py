@@ -133,6 +133,27 @@ lib.PogsAmdSolveManyFn.argtypes = [c_int, c_int, c_int, c_size_t, c_size_t, c_vo
                                    c_void_p, c_void_p]
 MANY_MIN_DIM_MAX = 512     # include/pogs_amd.h: POGS_AMD_MANY_MIN_DIM_MAX
 MANY_MAX_DIM_MAX = 16384   # include/pogs_amd.h: POGS_AMD_MANY_MAX_DIM_MAX
+
+
+class PogsAmdManyInfo(ctypes.Structure):
+    """include/pogs_amd.h: what PogsAmdManyGetInfo reports of a persistent many-problem handle."""
+    _fields_ = [("k", c_int), ("dtype", c_int), ("m", c_size_t), ("n", c_size_t), ("resident_bytes", c_size_t),
+                ("setup_s", c_double), ("loop_s", c_double), ("launches", ctypes.c_ulonglong),
+                ("problem_iters", ctypes.c_ulonglong), ("reserved", c_double * 8)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+MANY_COLD, MANY_WARM_GIVEN, MANY_WARM_LAST = 0, 1, 2   # include/pogs_amd.h: enum POGS_AMD_MANY_START
+lib.PogsAmdManyCreate.argtypes = [ctypes.POINTER(c_void_p), c_int, c_int, c_int, c_size_t, c_size_t, c_void_p, c_int,
+                                  ctypes.POINTER(PogsAmdOptions)]
+lib.PogsAmdManySolveFn.argtypes = [c_void_p, ctypes.POINTER(PogsAmdFn), ctypes.POINTER(PogsAmdFn), c_void_p, c_int,
+                                   c_void_p, c_void_p, c_double, c_double, c_uint, c_uint, c_int, c_int, c_void_p,
+                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+lib.PogsAmdManyGetInfo.argtypes = [c_void_p, ctypes.POINTER(PogsAmdManyInfo)]
+lib.PogsAmdManyDestroy.argtypes = [c_void_p]
+lib.PogsAmdManyDestroy.restype = None
 lib.PogsAmdBeginRunFn.argtypes = [c_void_p, ctypes.POINTER(PogsAmdFn), ctypes.POINTER(PogsAmdFn), c_double, c_double, c_double,
                                   c_uint, c_int, c_int]
 lib.PogsAmdBeginRun.argtypes = [c_void_p] + [c_void_p] * 12 + [c_double, c_double, c_double, c_uint, c_int, c_int]
@@ -206,7 +227,8 @@ def pool_trim(device=-1):
 ABI_SYMBOLS = [
     "PogsD", "PogsS", "PogsSparseD", "PogsSparseS",
     "PogsAmdDistUniqueId", "PogsAmdCreateDense", "PogsAmdCreateSparse", "PogsAmdSolve", "PogsAmdSolveFn", "PogsAmdSolveBatchFn", "PogsAmdSolveBatchSparseFn",
-    "PogsAmdSolveManyFn", "PogsAmdBeginRun", "PogsAmdBeginRunFn",
+    "PogsAmdSolveManyFn", "PogsAmdManyCreate", "PogsAmdManySolveFn", "PogsAmdManyGetInfo", "PogsAmdManyDestroy",
+    "PogsAmdBeginRun", "PogsAmdBeginRunFn",
     "PogsAmdIterate", "PogsAmdSetWarmStart", "PogsAmdGetStats", "PogsAmdResetStats", "PogsAmdDestroy", "PogsAmdLastError",
     "PogsAmdPoolStats", "PogsAmdPoolTrim",
     "PogsAmdProxEval", "PogsAmdFuncEval", "PogsAmdProjSubgradEval", "PogsAmdGetEquil", "PogsAmdProject", "PogsAmdMul", "PogsAmdRandUniform",

@@ -234,6 +234,10 @@ void prox_eval_host(size_t n, const int *h, const void *a, const void *b, const 
 
 using namespace pogs_amd;
 
+struct PogsAmdMany {
+  std::unique_ptr<ManyHandle> impl;
+};
+
 extern "C" {
 
 int PogsD(enum ORD ord, size_t m, size_t n, const double *A, const double *f_a, const double *f_b,
@@ -411,6 +415,53 @@ int PogsAmdSolveManyFn(int dtype, enum ORD ord, int k, size_t m, size_t n, const
                BatchOut{x, y, l, mu, optval, final_iter, status});
     return 0;
   });
+}
+
+int PogsAmdManyCreate(PogsAmdMany **out, int dtype, enum ORD ord, int k, size_t m, size_t n, const void *A, int mem,
+                      const PogsAmdOptions *opt) {
+  return guarded([&]() {
+    POGS_CHECK(out != nullptr, "many-problem handle: null out");
+    *out = nullptr;
+    POGS_CHECK(k >= 1, "many-problem solve: k must be >= 1");
+    const int projector = opt ? opt->projector : POGS_AMD_PROJ_DEFAULT;
+    POGS_CHECK(projector == POGS_AMD_PROJ_DEFAULT || projector == POGS_AMD_PROJ_DIRECT,
+               "many-problem solve: only the direct projector is supported (CGLS refused)");
+    std::unique_ptr<PogsAmdMany> h(new PogsAmdMany);
+    h->impl.reset(many_create(dtype, static_cast<int>(ord), k, m, n, A, mem, opt ? opt->device : -1));
+    *out = h.release();
+    return 0;
+  });
+}
+
+int PogsAmdManySolveFn(PogsAmdMany *h, const PogsAmdFn *f, const PogsAmdFn *g, const double *rho, int start,
+                       const void *x0, const void *l0, double abs_tol, double rel_tol, unsigned int max_iter,
+                       unsigned int verbose, int adaptive_rho, int gap_stop, void *x, void *y, void *l, void *mu,
+                       double *optval, unsigned int *final_iter, int *status, double *rho_final) {
+  return guarded([&]() {
+    POGS_CHECK(h && h->impl, "many-problem handle: null handle");
+    const auto fg = fn_hosts("many-problem handle", h->impl->count(), f, g, x, final_iter, status);
+    DeviceGuard guard(h->impl->device());
+    h->impl->solve(fg.first.data(), fg.second.data(), ManyStart{start, x0, l0, rho, rho_final},
+                   make_params(1.0, abs_tol, rel_tol, max_iter, verbose, adaptive_rho, gap_stop),
+                   BatchOut{x, y, l, mu, optval, final_iter, status});
+    return 0;
+  });
+}
+
+int PogsAmdManyGetInfo(const PogsAmdMany *h, PogsAmdManyInfo *out) {
+  return guarded([&]() {
+    POGS_CHECK(h && h->impl && out, "null argument");
+    *out = h->impl->info();
+    return 0;
+  });
+}
+
+void PogsAmdManyDestroy(PogsAmdMany *h) {
+  try {
+    if (!h) return;
+    DeviceGuard guard(h->impl ? h->impl->device() : -1);   // buffers are freed on the handle's device
+    delete h;
+  } catch (...) {}
 }
 
 int PogsAmdBeginRunFn(PogsAmdSolver *s, const PogsAmdFn *f, const PogsAmdFn *g, double rho, double abs_tol, double rel_tol,

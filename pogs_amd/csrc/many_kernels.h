@@ -17,4 +17,30 @@ void solve_many(int dtype, int ord, int k, size_t m, size_t n, const void *A, in
 void many_setup_check(int dtype, int ord, int k, size_t m, size_t n, const void *A, int mem, void *A_eq, void *d,
                       void *e, double *nrmA, void *W);
 
+// The argument checks solve_many and many_create share (k, dtype, ord, mem, A, the envelope); host only.
+void many_check_args(int dtype, int ord, int k, size_t m, size_t n, const void *A, int mem);
+
+// How a solve on a ManyHandle starts (PogsAmdManySolveFn): start is an enum POGS_AMD_MANY_START; x0, l0 HOST arrays
+// (WARM_GIVEN only); rho and rho_final may be null.
+struct ManyStart {
+  int start;
+  const void *x0, *l0;
+  const double *rho;
+  double *rho_final;
+};
+
+// The persistent many-problem handle (PogsAmdMany): k problems set up once, resident on the device.
+struct ManyHandle {
+  virtual ~ManyHandle() {}
+  virtual int device() const = 0;
+  virtual int count() const = 0;
+  // Throws Error on a refusal, before any output is written or any state of the handle is changed.
+  virtual void solve(const FnHost *f, const FnHost *g, const ManyStart &st, const SolveParams &p,
+                     const BatchOut &out) = 0;
+  virtual PogsAmdManyInfo info() const = 0;
+};
+
+// Checks as solve_many's (many_check_args), before any device work; then upload, setup, and the resident buffers.
+ManyHandle *many_create(int dtype, int ord, int k, size_t m, size_t n, const void *A, int mem, int device);
+
 }  // namespace pogs_amd

@@ -10,10 +10,14 @@
 // Every sum inside a problem runs in a fixed order that depends on (m, n) alone (fixed thread -> element maps,
 // fixed butterflies, partials combined in index order), and a problem's arithmetic never looks at its index, the
 // chunk or the other problems: its bytes are its own.
+//
+// The persistent handle (PogsAmdManyCreate / PogsAmdManySolveFn) runs the same setup once, keeps all k problems
+// resident and opens every solve with many_begin_kernel: cold, or warm from a problem's kept x, l and rho.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 #include "many_kernels.h"
@@ -535,6 +539,36 @@ __global__ __launch_bounds__(kTPB) void many_loop_kernel(ManyArgs<T> a, int iter
   if (threadIdx.x == 0) a.ctl[q] = c;
 }
 
+// The start of a solve on a persistent handle, before its first loop launch: the problem is live again, and its
+// iterate is the cold start (z = zt = 0: x, xt, y, yt are the vectors the loop reads before it writes them) or, where
+// warm[q] is set (warm == nullptr: every problem cold), the reference's SetInitX + SetInitLambda (pogs.cpp:144-156)
+// from the problem's kept un-scaled x and l (a.xo, a.lo): x = x0 / e, y = A x, t = l0 / d, xt = (-A^T t)(-1 / rho),
+// yt = t (-1 / rho), with the rho of the control block this solve starts from.  The sums are row_dots / col_dots with
+// the loop's maps.  grid: problems
+template <typename T>
+__global__ __launch_bounds__(kTPB) void many_begin_kernel(ManyArgs<T> a, const int *warm) {
+  __shared__ T part[kTPB];
+  const int q = blockIdx.x, m = a.m, n = a.n;
+  T *w = a.ws + q * a.stride;
+  const T *A = w + a.oA;
+  T *x = w + a.ox[kX], *xt = w + a.ox[kXt], *y = w + a.oy[kY], *yt = w + a.oy[kYt], *ytemp = w + a.oy[kYtemp];
+  const T *e = w + a.ox[kE], *d = w + a.oy[kD];
+  if (threadIdx.x == 0) a.st[q].stopped = 0;
+  if (!warm || !warm[q]) {
+    for (int j = threadIdx.x; j < n; j += kTPB) { x[j] = 0; xt[j] = 0; }
+    for (int i = threadIdx.x; i < m; i += kTPB) { y[i] = 0; yt[i] = 0; }
+    return;
+  }
+  const T *x0 = a.xo + static_cast<size_t>(q) * n, *l0 = a.lo + static_cast<size_t>(q) * m;
+  const T mr = static_cast<T>(-1) / a.ctl[q].rho;
+  for (int j = threadIdx.x; j < n; j += kTPB) x[j] = x0[j] / e[j];
+  for (int i = threadIdx.x; i < m; i += kTPB) ytemp[i] = l0[i] / d[i];
+  __syncthreads();
+  row_dots<T, false>(A, n, m, [&](int) { return n; }, x, [&](int i, T s) { y[i] = s; });
+  col_dots<T, false>(A, n, m, n, [](int) { return 0; }, ytemp, [&](int j, T s) { xt[j] = (-s) * mr; }, part);
+  for (int i = threadIdx.x; i < m; i += kTPB) yt[i] = ytemp[i] * mr;
+}
+
 // ---- host driver ------------------------------------------------------------------------------------
 
 size_t workspace_cap_bytes(int device) {
@@ -651,6 +685,94 @@ void many_setup_check_t(int ord, int kk, size_t m_, size_t n_, const void *Ain, 
     for (int q = 0; q < kk; ++q) nrmA[q] = static_cast<double>(hst[q].nrmA);
 }
 
+// ADMM iterations per loop launch: kMaxIterPerLaunch, fewer where an iteration streams much (kLaunchBytes).
+template <typename T>
+int many_iters_per_launch(size_t mn, int K) {
+  const double iter_bytes = (2.0 * static_cast<double>(mn) + static_cast<double>(K) * K) * sizeof(T);
+  return static_cast<int>(std::max(1.0, std::min<double>(kMaxIterPerLaunch, kLaunchBytes / iter_bytes)));
+}
+
+// The functions of cnt problems on their way to the device: per-element fields packed into one upload (tpool, hpool),
+// broadcast fields as values.  The host copies live here until the next run.
+template <typename T>
+struct ManyFnUpload {
+  std::vector<T> tp;
+  std::vector<int> hp;
+  std::vector<ManyFn<T>> fh;
+  void run(const FnHost *f, const FnHost *g, int cnt, size_t m_, size_t n_, T *tpool, int *hpool, ManyFn<T> *fnd,
+           hipStream_t s) {
+    tp.clear();
+    hp.clear();
+    fh.resize(2 * static_cast<size_t>(cnt));
+    for (int q = 0; q < cnt; ++q) {
+      for (int side = 0; side < 2; ++side) {
+        const FnHost &fn = side == 0 ? f[q] : g[q];
+        const size_t len = side == 0 ? m_ : n_;
+        warn_negative_coeffs<T>(fn, len);
+        ManyFn<T> &d = fh[2 * q + side];
+        const void *ptr[5] = {fn.a, fn.b, fn.c, fn.d, fn.e};
+        for (int fld = 0; fld < 5; ++fld) {
+          d.v[fld] = static_cast<T>(fn.s0[fld]);
+          d.p[fld] = nullptr;
+          if (ptr[fld]) {
+            d.p[fld] = tpool + tp.size();
+            const T *src_f = static_cast<const T *>(ptr[fld]);
+            tp.insert(tp.end(), src_f, src_f + len);
+          }
+        }
+        d.h0 = fn.h0;
+        d.h = nullptr;
+        if (fn.h) {
+          d.h = hpool + hp.size();
+          hp.insert(hp.end(), fn.h, fn.h + len);
+        }
+      }
+    }
+    if (!tp.empty()) POGS_HIP_CHECK(hipMemcpyAsync(tpool, tp.data(), tp.size() * sizeof(T), hipMemcpyHostToDevice, s));
+    if (!hp.empty()) POGS_HIP_CHECK(hipMemcpyAsync(hpool, hp.data(), hp.size() * sizeof(int), hipMemcpyHostToDevice, s));
+    POGS_HIP_CHECK(hipMemcpyAsync(fnd, fh.data(), 2 * static_cast<size_t>(cnt) * sizeof(ManyFn<T>), hipMemcpyHostToDevice,
+                                  s));
+  }
+};
+
+// The loop of cnt problems (a.done_count zeroed on the stream before): every launch advances each live problem by at
+// most ipl iterations, and the host reads one done-count per launch.  Returns the number of launches.
+template <typename T>
+unsigned long long many_run_loop(const ManyArgs<T> &a, int cnt, int ipl, unsigned max_iter, unsigned *hdone,
+                                 hipStream_t s) {
+  const unsigned long long max_launches = (max_iter + ipl - 1) / ipl + 1;
+  unsigned long long nl = 0;
+  for (;;) {
+    hipLaunchKernelGGL(many_loop_kernel<T>, dim3(cnt), dim3(kTPB), 0, s, a, ipl);
+    POGS_HIP_CHECK(hipGetLastError());
+    ++nl;
+    POGS_HIP_CHECK(hipMemcpyAsync(hdone, a.done_count, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    POGS_HIP_CHECK(hipStreamSynchronize(s));
+    if (*hdone >= static_cast<unsigned>(cnt)) break;
+    POGS_CHECK(nl < max_launches, "many-problem solve: a problem did not stop within max_iter iterations");
+  }
+  return nl;
+}
+
+// The one summary line of a call (verbose > 0).  head: what precedes "; status".
+inline void many_print_summary(const char *head, int k, const unsigned *final_iter, const int *status, double t_setup,
+                               double t_loop, double t_total, unsigned long long launches) {
+  int counts[7] = {0, 0, 0, 0, 0, 0, 0};
+  unsigned it_lo = ~0u, it_hi = 0;
+  for (int q = 0; q < k; ++q) {
+    const int st = status[q];
+    ++counts[st >= 0 && st < 7 ? st : 6];
+    it_lo = std::min(it_lo, final_iter[q]);
+    it_hi = std::max(it_hi, final_iter[q]);
+  }
+  std::printf("%s; status", head);
+  for (int st = 0; st < 7; ++st)
+    if (counts[st]) std::printf(" %s: %d,", status_string(st), counts[st]);
+  std::printf(" iterations %u..%u; setup %.3e s, loop %.3e s, total %.3e s; %llu launches\n", it_lo, it_hi, t_setup,
+              t_loop, t_total, launches);
+  std::fflush(stdout);
+}
+
 template <typename T>
 void solve_many_t(int ord, int kk, size_t m_, size_t n_, const void *Ain, int mem, int device, const FnHost *f,
                   const FnHost *g, const double *rho0, const SolveParams &p, const BatchOut &out) {
@@ -685,17 +807,12 @@ void solve_many_t(int ord, int kk, size_t m_, size_t n_, const void *Ain, int me
   a.ws = ws.p; a.rnd = rnd.p; a.fn = fnd.p; a.ctl = ctld.p; a.st = std_.p; a.done_count = done.p;
   a.xo = xo.p; a.yo = yo.p; a.lo = lo.p; a.muo = muo.p; a.optval = optv.p; a.iters = iters.p; a.status = stat.p;
 
-  const double iter_bytes = (2.0 * static_cast<double>(mn) + static_cast<double>(K) * K) * sizeof(T);
-  const int ipl = static_cast<int>(std::max(1.0, std::min<double>(kMaxIterPerLaunch, kLaunchBytes / iter_bytes)));
+  const int ipl = many_iters_per_launch<T>(mn, K);
 
-  std::vector<T> tp;
-  std::vector<int> hp;
-  std::vector<ManyFn<T>> fh(2 * static_cast<size_t>(chunk));
+  ManyFnUpload<T> up;
   std::vector<AdmmControl<T>> ch(chunk);
   unsigned long long launches = 0;
   double t_setup = 0, t_loop = 0;
-  int counts[7] = {0, 0, 0, 0, 0, 0, 0};
-  unsigned it_lo = ~0u, it_hi = 0;
   for (int j0 = 0; j0 < kk; j0 += chunk) {
     const int cnt = std::min(chunk, kk - j0);
     const double tc0 = wall_s();
@@ -705,37 +822,7 @@ void solve_many_t(int ord, int kk, size_t m_, size_t n_, const void *Ain, int me
       src = stage.p;
     }
     a.src = src;
-    // the functions: per-element fields packed into one upload, broadcast fields as values
-    tp.clear();
-    hp.clear();
-    for (int q = 0; q < cnt; ++q) {
-      for (int side = 0; side < 2; ++side) {
-        const FnHost &fn = side == 0 ? f[j0 + q] : g[j0 + q];
-        const size_t len = side == 0 ? m_ : n_;
-        warn_negative_coeffs<T>(fn, len);
-        ManyFn<T> &d = fh[2 * q + side];
-        const void *ptr[5] = {fn.a, fn.b, fn.c, fn.d, fn.e};
-        for (int fld = 0; fld < 5; ++fld) {
-          d.v[fld] = static_cast<T>(fn.s0[fld]);
-          d.p[fld] = nullptr;
-          if (ptr[fld]) {
-            d.p[fld] = tpool.p + tp.size();
-            const T *src_f = static_cast<const T *>(ptr[fld]);
-            tp.insert(tp.end(), src_f, src_f + len);
-          }
-        }
-        d.h0 = fn.h0;
-        d.h = nullptr;
-        if (fn.h) {
-          d.h = hpool.p + hp.size();
-          hp.insert(hp.end(), fn.h, fn.h + len);
-        }
-      }
-    }
-    if (!tp.empty()) POGS_HIP_CHECK(hipMemcpyAsync(tpool.p, tp.data(), tp.size() * sizeof(T), hipMemcpyHostToDevice, s));
-    if (!hp.empty()) POGS_HIP_CHECK(hipMemcpyAsync(hpool.p, hp.data(), hp.size() * sizeof(int), hipMemcpyHostToDevice, s));
-    POGS_HIP_CHECK(hipMemcpyAsync(fnd.p, fh.data(), 2 * static_cast<size_t>(cnt) * sizeof(ManyFn<T>),
-                                  hipMemcpyHostToDevice, s));
+    up.run(f + j0, g + j0, cnt, m_, n_, tpool.p, hpool.p, fnd.p, s);
     for (int q = 0; q < cnt; ++q) ch[q] = make_admm_control<T>(p, rho0 ? rho0[j0 + q] : 1.0, m_, n_);
     POGS_HIP_CHECK(hipMemcpyAsync(ctld.p, ch.data(), static_cast<size_t>(cnt) * sizeof(AdmmControl<T>),
                                   hipMemcpyHostToDevice, s));
@@ -745,18 +832,7 @@ void solve_many_t(int ord, int kk, size_t m_, size_t n_, const void *Ain, int me
     const double tc1 = wall_s();
     t_setup += tc1 - tc0;
     // the loop: every launch advances each live problem by at most ipl iterations
-    const unsigned long long max_launches = (p.max_iter + ipl - 1) / ipl + 1;
-    unsigned long long nl = 0;
-    for (;;) {
-      hipLaunchKernelGGL(many_loop_kernel<T>, dim3(cnt), dim3(kTPB), 0, s, a, ipl);
-      POGS_HIP_CHECK(hipGetLastError());
-      ++launches;
-      ++nl;
-      POGS_HIP_CHECK(hipMemcpyAsync(hdone.p, done.p, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-      POGS_HIP_CHECK(hipStreamSynchronize(s));
-      if (*hdone.p >= static_cast<unsigned>(cnt)) break;
-      POGS_CHECK(nl < max_launches, "many-problem solve: a problem did not stop within max_iter iterations");
-    }
+    launches += many_run_loop(a, cnt, ipl, p.max_iter, hdone.p, s);
     t_loop += wall_s() - tc1;
     // outputs of the chunk
     auto d2h = [&](void *dst, const void *srcd, size_t bytes) {
@@ -771,28 +847,179 @@ void solve_many_t(int ord, int kk, size_t m_, size_t n_, const void *Ain, int me
     d2h(out.final_iter + j0, iters.p, cnt * sizeof(unsigned));
     d2h(out.status + j0, stat.p, cnt * sizeof(int));
     POGS_HIP_CHECK(hipStreamSynchronize(s));
-    for (int q = 0; q < cnt; ++q) {
-      const int st = out.status[j0 + q];
-      ++counts[st >= 0 && st < 7 ? st : 6];
-      it_lo = std::min(it_lo, out.final_iter[j0 + q]);
-      it_hi = std::max(it_hi, out.final_iter[j0 + q]);
-    }
   }
   if (p.verbose > 0) {
-    std::printf("POGS-AMD many: %d problems of %d x %d (%s), %d per chunk; status", kk, m, n,
-                sizeof(T) == 8 ? "fp64" : "fp32", chunk);
-    for (int st = 0; st < 7; ++st)
-      if (counts[st]) std::printf(" %s: %d,", status_string(st), counts[st]);
-    std::printf(" iterations %u..%u; setup %.3e s, loop %.3e s, total %.3e s; %llu launches\n", it_lo, it_hi, t_setup,
-                t_loop, wall_s() - t0, launches);
-    std::fflush(stdout);
+    char head[160];
+    std::snprintf(head, sizeof(head), "POGS-AMD many: %d problems of %d x %d (%s), %d per chunk", kk, m, n,
+                  sizeof(T) == 8 ? "fp64" : "fp32", chunk);
+    many_print_summary(head, kk, out.final_iter, out.status, t_setup, t_loop, wall_s() - t0, launches);
   }
 }
 
+
+// The persistent handle (PogsAmdMany): setup once for all k problems in one resident workspace, then any number of
+// solves, each opened by many_begin_kernel.  xo / lo double as the kept last solution the warm starts read.
+template <typename T>
+class ManyHandleT : public ManyHandle {
+ public:
+  ManyHandleT(int ord, int kk, size_t m, size_t n, const void *Ain, int mem, int device) : k_(kk), m_(m), n_(n) {
+    const double t0 = wall_s();
+    ctx_.init(device, 0);
+    hipStream_t s = ctx_.stream;
+    many_layout(a_, ord, m, n);
+    const size_t kz = static_cast<size_t>(kk), mn = m * n, len = m + n;
+    std::memset(&info_, 0, sizeof(info_));
+    info_.k = kk; info_.dtype = sizeof(T) == 8 ? POGS_AMD_F64 : POGS_AMD_F32; info_.m = m; info_.n = n;
+    info_.resident_bytes = kz * (sizeof(T) * (a_.stride + 2 * len + 5 * len + 1) + sizeof(int) * (len + 2) +
+                                 sizeof(double) + sizeof(unsigned) + 2 * sizeof(ManyFn<T>) + sizeof(AdmmControl<T>) +
+                                 sizeof(ManyState<T>));
+    try {
+      ws_.alloc(kz * a_.stride);
+      xo_.alloc(kz * n); yo_.alloc(kz * m); lo_.alloc(kz * m); muo_.alloc(kz * n);
+      optv_.alloc(kz); iters_.alloc(kz); stat_.alloc(kz); warm_.alloc(kz); done_.alloc(1);
+      fnd_.alloc(2 * kz); ctld_.alloc(kz); st_.alloc(kz);
+      tpool_.alloc(kz * 5 * len + 1); hpool_.alloc(kz * len + 1);
+    } catch (const std::exception &e) {
+      (void)hipGetLastError();
+      char buf[512];
+      std::snprintf(buf, sizeof(buf),
+                    "many-problem handle: the resident footprint of %d problems of %zu x %zu (%.1f MB) cannot be "
+                    "allocated; PogsAmdSolveManyFn solves them in chunks [%s]",
+                    kk, m, n, static_cast<double>(info_.resident_bytes) / (1 << 20), e.what());
+      throw Error(buf);
+    }
+    hdone_.alloc(1);
+    a_.ws = ws_.p; a_.fn = fnd_.p; a_.ctl = ctld_.p; a_.st = st_.p; a_.done_count = done_.p;
+    a_.xo = xo_.p; a_.yo = yo_.p; a_.lo = lo_.p; a_.muo = muo_.p; a_.optval = optv_.p; a_.iters = iters_.p;
+    a_.status = stat_.p;
+    // setup in chunks: a host A through a staging buffer under the workspace cap; a chunk is also the y extent of
+    // the copy and Gram grids
+    size_t chunk = std::min<size_t>(kz, 32768);
+    if (mem == POGS_AMD_HOST)
+      chunk = std::max<size_t>(1, std::min(chunk, workspace_cap_bytes(ctx_.device) / (mn * sizeof(T))));
+    DevBuf<T> stage, rnd(n);
+    if (mem == POGS_AMD_HOST) stage.alloc(chunk * mn);
+    many_start_vector(rnd.p, n, s);
+    for (size_t j0 = 0; j0 < kz; j0 += chunk) {
+      const int cnt = static_cast<int>(std::min(chunk, kz - j0));
+      ManyArgs<T> c = a_;
+      c.ws = ws_.p + j0 * a_.stride;
+      c.st = st_.p + j0;
+      c.rnd = rnd.p;
+      c.src = static_cast<const T *>(Ain) + j0 * mn;
+      if (mem == POGS_AMD_HOST) {
+        POGS_HIP_CHECK(hipMemcpyAsync(stage.p, c.src, static_cast<size_t>(cnt) * mn * sizeof(T), hipMemcpyHostToDevice, s));
+        c.src = stage.p;
+      }
+      many_setup(c, cnt, s);
+    }
+    ctx_.sync();
+    ipl_ = many_iters_per_launch<T>(mn, a_.k);
+    last_status_.assign(kz, POGS_ERROR);
+    last_rho_.assign(kz, 1.0);
+    info_.setup_s = wall_s() - t0;
+  }
+  ~ManyHandleT() override { (void)hipStreamSynchronize(ctx_.stream); }
+
+  int device() const override { return ctx_.device; }
+  int count() const override { return k_; }
+  PogsAmdManyInfo info() const override { return info_; }
+
+  void solve(const FnHost *f, const FnHost *g, const ManyStart &sa, const SolveParams &p, const BatchOut &out) override {
+    POGS_CHECK(out.x && out.final_iter && out.status, "many-problem handle: x, final_iter and status must not be NULL");
+    POGS_CHECK(sa.start == POGS_AMD_MANY_COLD || sa.start == POGS_AMD_MANY_WARM_GIVEN ||
+               sa.start == POGS_AMD_MANY_WARM_LAST, "many-problem handle: unknown start mode");
+    POGS_CHECK(sa.start != POGS_AMD_MANY_WARM_GIVEN || (sa.x0 && sa.l0),
+               "many-problem handle: a given warm start needs both x0 and l0 (pogs.cpp:159-179)");
+    POGS_CHECK(sa.start != POGS_AMD_MANY_WARM_LAST || solved_,
+               "many-problem handle: start = last before the handle's first solve");
+    const double t0 = wall_s();
+    hipStream_t s = ctx_.stream;
+    const size_t kz = static_cast<size_t>(k_);
+    const size_t xb = kz * n_ * sizeof(T), yb = kz * m_ * sizeof(T);
+    up_.run(f, g, k_, m_, n_, tpool_.p, hpool_.p, fnd_.p, s);
+    ch_.resize(kz);
+    hwarm_.resize(kz);
+    for (size_t q = 0; q < kz; ++q) {
+      const bool kept = last_status_[q] == POGS_SUCCESS || last_status_[q] == POGS_MAX_ITER;
+      hwarm_[q] = sa.start == POGS_AMD_MANY_WARM_GIVEN || (sa.start == POGS_AMD_MANY_WARM_LAST && kept);
+      double rho = sa.rho ? sa.rho[q] : 1.0;
+      if (sa.start == POGS_AMD_MANY_WARM_LAST) rho = !kept ? 1.0 : sa.rho ? sa.rho[q] : last_rho_[q];
+      ch_[q] = make_admm_control<T>(p, rho, m_, n_);
+    }
+    POGS_HIP_CHECK(hipMemcpyAsync(ctld_.p, ch_.data(), kz * sizeof(AdmmControl<T>), hipMemcpyHostToDevice, s));
+    const int *warm = nullptr;
+    if (sa.start != POGS_AMD_MANY_COLD) {
+      POGS_HIP_CHECK(hipMemcpyAsync(warm_.p, hwarm_.data(), kz * sizeof(int), hipMemcpyHostToDevice, s));
+      warm = warm_.p;
+    }
+    if (sa.start == POGS_AMD_MANY_WARM_GIVEN) {
+      POGS_HIP_CHECK(hipMemcpyAsync(xo_.p, sa.x0, xb, hipMemcpyHostToDevice, s));
+      POGS_HIP_CHECK(hipMemcpyAsync(lo_.p, sa.l0, yb, hipMemcpyHostToDevice, s));
+    }
+    POGS_HIP_CHECK(hipMemsetAsync(done_.p, 0, sizeof(unsigned), s));
+    ctx_.sync();
+    const double t1 = wall_s();
+    hipLaunchKernelGGL(many_begin_kernel<T>, dim3(k_), dim3(kTPB), 0, s, a_, warm);
+    POGS_HIP_CHECK(hipGetLastError());
+    const unsigned long long launches = 1 + many_run_loop(a_, k_, ipl_, p.max_iter, hdone_.p, s);
+    const double t_loop = wall_s() - t1;
+    auto d2h = [&](void *dst, const void *srcd, size_t bytes) {
+      POGS_HIP_CHECK(hipMemcpyAsync(dst, srcd, bytes, hipMemcpyDeviceToHost, s));
+    };
+    d2h(out.x, xo_.p, xb);
+    if (out.y) d2h(out.y, yo_.p, yb);
+    if (out.l) d2h(out.l, lo_.p, yb);
+    if (out.mu) d2h(out.mu, muo_.p, xb);
+    if (out.optval) d2h(out.optval, optv_.p, kz * sizeof(double));
+    d2h(out.final_iter, iters_.p, kz * sizeof(unsigned));
+    d2h(out.status, stat_.p, kz * sizeof(int));
+    d2h(ch_.data(), ctld_.p, kz * sizeof(AdmmControl<T>));
+    POGS_HIP_CHECK(hipStreamSynchronize(s));
+    unsigned long long piters = 0;
+    for (size_t q = 0; q < kz; ++q) {
+      last_status_[q] = out.status[q];
+      last_rho_[q] = static_cast<double>(ch_[q].rho);
+      if (sa.rho_final) sa.rho_final[q] = last_rho_[q];
+      piters += out.final_iter[q] + 1ull;
+    }
+    solved_ = true;
+    info_.loop_s = t_loop;
+    info_.launches = launches;
+    info_.problem_iters = piters;
+    if (p.verbose > 0) {
+      static const char *const kStart[3] = {"cold", "warm (given)", "warm (last)"};
+      char head[200];
+      std::snprintf(head, sizeof(head), "POGS-AMD many handle: %d problems of %d x %d (%s), start %s", k_,
+                    static_cast<int>(m_), static_cast<int>(n_), sizeof(T) == 8 ? "fp64" : "fp32", kStart[sa.start]);
+      many_print_summary(head, k_, out.final_iter, out.status, 0.0, t_loop, wall_s() - t0, launches);
+    }
+  }
+
+ private:
+  Ctx ctx_;
+  ManyArgs<T> a_{};
+  int k_, ipl_ = 1;
+  size_t m_, n_;
+  DevBuf<T> ws_, xo_, yo_, lo_, muo_, tpool_;
+  DevBuf<double> optv_;
+  DevBuf<unsigned> iters_, done_;
+  DevBuf<int> stat_, hpool_, warm_;
+  DevBuf<ManyFn<T>> fnd_;
+  DevBuf<AdmmControl<T>> ctld_;
+  DevBuf<ManyState<T>> st_;
+  PinnedBuf<unsigned> hdone_;
+  ManyFnUpload<T> up_;
+  std::vector<AdmmControl<T>> ch_;
+  std::vector<int> hwarm_, last_status_;   // each problem's status after the last solve (POGS_ERROR: none yet)
+  std::vector<double> last_rho_;           // and the rho it stopped at
+  bool solved_ = false;
+  PogsAmdManyInfo info_;
+};
+
 }  // namespace
 
-void solve_many(int dtype, int ord, int k, size_t m, size_t n, const void *A, int mem, int device, const FnHost *f,
-                const FnHost *g, const double *rho, const SolveParams &p, const BatchOut &out) {
+void many_check_args(int dtype, int ord, int k, size_t m, size_t n, const void *A, int mem) {
   POGS_CHECK(dtype == POGS_AMD_F32 || dtype == POGS_AMD_F64, "many-problem solve: unknown dtype");
   POGS_CHECK(k >= 1, "many-problem solve: k must be >= 1");
   POGS_CHECK(ord == ROW_MAJ || ord == COL_MAJ, "many-problem solve: unknown ord");
@@ -801,6 +1028,18 @@ void solve_many(int dtype, int ord, int k, size_t m, size_t n, const void *A, in
   POGS_CHECK(m >= 1 && n >= 1, "many-problem solve: m and n must be >= 1");
   POGS_CHECK(std::min(m, n) <= POGS_AMD_MANY_MIN_DIM_MAX, "many-problem solve: min(m, n) exceeds POGS_AMD_MANY_MIN_DIM_MAX");
   POGS_CHECK(std::max(m, n) <= POGS_AMD_MANY_MAX_DIM_MAX, "many-problem solve: max(m, n) exceeds POGS_AMD_MANY_MAX_DIM_MAX");
+}
+
+ManyHandle *many_create(int dtype, int ord, int k, size_t m, size_t n, const void *A, int mem, int device) {
+  many_check_args(dtype, ord, k, m, n, A, mem);
+  DeviceGuard guard(device);
+  if (dtype == POGS_AMD_F64) return new ManyHandleT<double>(ord, k, m, n, A, mem, device);
+  return new ManyHandleT<float>(ord, k, m, n, A, mem, device);
+}
+
+void solve_many(int dtype, int ord, int k, size_t m, size_t n, const void *A, int mem, int device, const FnHost *f,
+                const FnHost *g, const double *rho, const SolveParams &p, const BatchOut &out) {
+  many_check_args(dtype, ord, k, m, n, A, mem);
   POGS_CHECK(out.x && out.final_iter && out.status, "many-problem solve: x, final_iter and status must not be NULL");
   if (dtype == POGS_AMD_F64) solve_many_t<double>(ord, k, m, n, A, mem, device, f, g, rho, p, out);
   else solve_many_t<float>(ord, k, m, n, A, mem, device, f, g, rho, p, out);

@@ -737,6 +737,113 @@ class Solver:
         self.close()
 
 
+class ManySolver:
+    """`solve_many`'s k problems kept on the GPU: every matrix is equilibrated and factored once, then re-solved
+    with new functions (include/pogs_amd.h: PogsAmdManyCreate / PogsAmdManySolveFn).
+
+    ``A`` as `solve_many` takes it; the handle owns its copy (a device tensor is read during construction only).
+    All k problems stay resident: a set that does not fit is refused, `solve_many` solves such a set in chunks."""
+
+    _STARTS = {"cold": _lib.MANY_COLD, "warm": _lib.MANY_WARM_GIVEN, "last": _lib.MANY_WARM_LAST}
+
+    def __init__(self, A, dtype=None, device=-1):
+        self._h = ctypes.c_void_p()
+        k, m, n, aptr, mem, order, dt, tdev, keep_a = _many_matrices(A, dtype)
+        self.k, self.m, self.n, self.dtype = k, m, n, np.dtype(dt)
+        dev = tdev if (device == -1 and tdev is not None) else device
+        opt = _lib.PogsAmdOptions(device=dev, projector=_lib.PROJ_DIRECT)
+        code = _lib.F64 if self.dtype == np.float64 else _lib.F32
+        st = lib.PogsAmdManyCreate(ctypes.byref(self._h), code, int(order), k, m, n, aptr, mem, ctypes.byref(opt))
+        del keep_a
+        if st != 0:
+            self._h = ctypes.c_void_p()
+            raise RuntimeError("pogs_amd: many-problem handle creation failed: " + _lib.last_error())
+        _LIVE_SOLVERS.add(self)
+
+    def solve(self, fs, gs, rho=None, start="cold", x0=None, l0=None, abs_tol=1e-4, rel_tol=1e-4, max_iter=2500,
+              verbose=0, adaptive_rho=True, gap_stop=True):
+        """Solve the k problems with (fs[j], gs[j]).  ``start``: "cold" (z = 0), "warm" (from ``x0``: k x n and
+        ``l0``: k x m, the reference's SetInitX + SetInitLambda per problem) or "last" (from each problem's own last
+        solution, kept on the device).  ``rho``: None, one value or k values; None means 1.0, and with "last" each
+        problem's final rho of the last solve.  Returns `solve_many`'s dictionary plus 'rho', the final rho per
+        problem."""
+        k, m, n, dt = self.k, self.m, self.n, self.dtype
+        if not self._h:
+            raise ValueError("ManySolver: the handle is closed")
+        if start not in self._STARTS:
+            raise ValueError("ManySolver: start must be 'cold', 'warm' or 'last', got %r" % (start,))
+        fs, gs = list(fs), list(gs)
+        if len(fs) != k or len(gs) != k:
+            raise ValueError("ManySolver: %d matrices, %d f and %d g function vectors" % (k, len(fs), len(gs)))
+        if start == "warm":
+            if x0 is None or l0 is None:
+                raise ValueError("ManySolver: start='warm' needs both x0 (k x n) and l0 (k x m)")
+            x0 = np.ascontiguousarray(x0, dtype=dt)
+            l0 = np.ascontiguousarray(l0, dtype=dt)
+            if x0.shape != (k, n) or l0.shape != (k, m):
+                raise ValueError("ManySolver: x0 must be %d x %d and l0 %d x %d, got %s and %s"
+                                 % (k, n, k, m, x0.shape, l0.shape))
+        elif x0 is not None or l0 is not None:
+            raise ValueError("ManySolver: x0 / l0 are read with start='warm' only")
+        rhos = None
+        if rho is not None:
+            rhos = np.full(k, float(rho)) if np.ndim(rho) == 0 else np.ascontiguousarray(rho, dtype=np.float64).ravel()
+            if len(rhos) != k:
+                raise ValueError("ManySolver: %d problems and %d rho values" % (k, len(rhos)))
+        keep = []
+        fa = (_lib.PogsAmdFn * k)()
+        ga = (_lib.PogsAmdFn * k)()
+        for j in range(k):
+            if len(fs[j]) != m or len(gs[j]) != n:
+                raise ValueError("ManySolver: f must have length %d and g length %d, got %d and %d"
+                                 % (m, n, len(fs[j]), len(gs[j])))
+            fa[j] = _fn_struct(fs[j], m, dt, keep)
+            ga[j] = _fn_struct(gs[j], n, dt, keep)
+        x = np.zeros((k, n), dt)
+        y = np.zeros((k, m), dt)
+        l = np.zeros((k, m), dt)
+        mu = np.zeros((k, n), dt)
+        optval = np.zeros(k, np.float64)
+        final_iter = np.zeros(k, np.uint32)
+        status = np.zeros(k, np.int32)
+        rho_final = np.zeros(k, np.float64)
+        st = lib.PogsAmdManySolveFn(self._h, fa, ga, None if rhos is None else _ptr(rhos), self._STARTS[start],
+                                    None if x0 is None else _ptr(x0), None if l0 is None else _ptr(l0), abs_tol,
+                                    rel_tol, int(max_iter), int(verbose), int(adaptive_rho), int(gap_stop), _ptr(x),
+                                    _ptr(y), _ptr(l), _ptr(mu), _ptr(optval), _ptr(final_iter), _ptr(status),
+                                    _ptr(rho_final))
+        del keep
+        if st != 0:
+            raise RuntimeError("pogs_amd: many-problem solve failed: " + _lib.last_error())
+        return {"x": x, "y": y, "l": l, "mu": mu, "optval": optval, "iterations": final_iter.astype(np.int64),
+                "status": status.astype(np.int64), "rho": rho_final}
+
+    def info(self):
+        """k, m, n, dtype code, resident bytes, create's setup seconds and the last solve's loop seconds, launches
+        and problem-iterations (include/pogs_amd.h: PogsAmdManyInfo)."""
+        out = _lib.PogsAmdManyInfo()
+        if lib.PogsAmdManyGetInfo(self._h, ctypes.byref(out)) != 0:
+            raise RuntimeError("pogs_amd: " + _lib.last_error())
+        return out.as_dict()
+
+    def close(self):
+        if self._h:
+            lib.PogsAmdManyDestroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 def prox_eval(f, rho, v, dtype=None):
     """Element-wise ProxEval on the GPU (reference: src/include/prox_lib.h:207-230)."""
     dt = _resolve_dtype(dtype)
