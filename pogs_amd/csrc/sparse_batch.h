@@ -2,7 +2,7 @@
 // product with A or A^T shared by all of them (one GPU, tall or wide, CSR or CSC input).
 //
 // The equilibration and the norm estimate depend on A only, so K graph-form problems on one matrix can run their
-// ADMM iterations side by side.  Each product reads the handle's equilibrated plain CSR copy (A_ for A v, At_ for
+// ADMM iterations side by side.  Each product reads the operator's equilibrated plain CSR copy (A() for A v, At() for
 // A^T v) once and forms the K dot products of every row from it (sparse_batch_kernels.hip); the K operands are packed
 // interleaved, [col][Kp], so the K values of a column are one gather.  The projection is a batched CGLS: every
 // member runs its own CG (shift 1, at most 500 steps, its own AdmmControl::proj_tol(), warm-started from its previous
@@ -31,8 +31,9 @@ void SparseSolver<T>::solve_batch_sparse(int kb, const FnHost *f, const FnHost *
   for (DevBuf<T> *b : {&cr, &cq, &cp, &cs}) b->zero(s);
   DevBuf<T> pk(static_cast<size_t>(std::max(m, n)) * kBatchMax);   // interleaved operands [col][Kp]
   // product geometry: from the matrix only (the same for every k and slot)
-  const SpBatchCsr<T> MA = sp_batch_geometry(A_.val.p, A_.ind.p, A_.ptr.p, m, nnz_, ctx_.num_cu);
-  const SpBatchCsr<T> MT = sp_batch_geometry(At_.val.p, At_.ind.p, At_.ptr.p, n, nnz_, ctx_.num_cu);
+  const DevCsr<T> &A = op_->A(), &At = op_->At();
+  const SpBatchCsr<T> MA = sp_batch_geometry(A.val.p, A.ind.p, A.ptr.p, m, nnz_, ctx_.num_cu);
+  const SpBatchCsr<T> MT = sp_batch_geometry(At.val.p, At.ind.p, At.ptr.p, n, nnz_, ctx_.num_cu);
   const int vbx = B.vbx, vby = B.vby;
   DevBuf<double> qpart(static_cast<size_t>(kb) * MA.grid), spart(static_cast<size_t>(kb) * MT.grid),
       xpart(static_cast<size_t>(kb) * vbx), ppart(static_cast<size_t>(kb) * vbx), bC(static_cast<size_t>(kb) * kBatchRec),

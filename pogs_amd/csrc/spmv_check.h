@@ -1,6 +1,7 @@
 #pragma once
 // PogsAmdSpmvCheck (include/pogs_amd.h, Part 3): one product of the solo sparse solver on HOST arrays, on copies built
-// by SparseSolver's own build_structure / build_sell / refill_sell (sparse.hip), without the equilibration.
+// by the solver's own SparseOperator (sparse_operator.h: structure, tiled copies, scale, finalize_values), with no solver
+// and no equilibration around it.  spmv_check() itself is in sparse.hip.
 #include <cstddef>
 
 namespace pogs_amd {

@@ -1,7 +1,8 @@
 """The product of the solo sparse solver on its own -- both CSR copies (the second transposed on the device), the tiled
 lane-stream copies (csrc/sell.h) in both storage formats, the plain CSR kernel, the column-group reduction -- through
-PogsAmdSpmvCheck (include/pogs_amd.h, Part 3), which runs SparseSolver's own build_structure / build_sell / refill_sell /
-spmv on HOST arrays without the equilibration, against references formed in fp64 (fp32 data) or long double (fp64 data).
+PogsAmdSpmvCheck (include/pogs_amd.h, Part 3), which runs the solver's own SparseOperator (csrc/sparse_operator.h: its
+build_structure / build_sell, scale, finalize_values and spmv) on HOST arrays without a solver and without the
+equilibration, against references formed in fp64 (fp32 data) or long double (fp64 data).
 
 Every case names the path it must reach and asserts it from `info`, so a case that stops reaching its path fails.
 num_cu = 256 in every case; BW x RR = 18432 x 16384 (fp32), 12288 x 6144 (fp64): columns per block, rows per range.
