@@ -412,6 +412,11 @@ int PogsAmdReadBandwidth(int device, size_t bytes, int reps, double *gb_per_s, i
  * (alu) and by the butterfly through the LDS crossbar (lds): the two must agree bit for bit
  * (tests/test_gpu_dense.py). */
 int PogsAmdWaveSumCheck(int dtype, size_t n, const void *in_host, void *alu_host, void *lds_host);
+/* Diagnostic: the logical workgroup ids of the dense one-pass iteration kernels (csrc/stream.h: logical_block_id),
+ * which deal rows and partial-sum slots by them.  Launches `grid` workgroups and returns ids_host[b] = the id that
+ * block b computed: a permutation of 0 .. grid - 1 for every grid.  *group: blocks whose index agrees modulo this
+ * number take consecutive ids (0: built with blockIdx.x as the id).  tests/test_gpu_block_ids.py. */
+int PogsAmdBlockIdCheck(int grid, int *ids_host, int *group);
 
 /* Diagnostics of the batched and many-problem kernels.  Every array is a HOST pointer of type dtype (0 fp32,
  * 1 fp64) unless noted; each entry uploads its inputs, runs the launch functions and geometry the solvers call, and

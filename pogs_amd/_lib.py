@@ -173,6 +173,7 @@ lib.PogsAmdMul.argtypes = [c_void_p, c_char, c_double, c_void_p, c_double, c_voi
 lib.PogsAmdRandUniform.argtypes = [c_int, c_size_t, c_void_p]
 lib.PogsAmdReadBandwidth.argtypes = [c_int, c_size_t, c_int, ctypes.POINTER(c_double), ctypes.POINTER(c_int)]
 lib.PogsAmdWaveSumCheck.argtypes = [c_int, c_size_t, c_void_p, c_void_p, c_void_p]
+lib.PogsAmdBlockIdCheck.argtypes = [c_int, c_void_p, ctypes.POINTER(c_int)]
 lib.PogsAmdBatchRowsCheck.argtypes = [c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_int, c_void_p, c_int,
                                       c_void_p, c_size_t, c_void_p, c_size_t]
 lib.PogsAmdBatchColsCheck.argtypes = [c_int, c_int, c_int, c_void_p, c_size_t, c_int, c_void_p, c_int, c_void_p,
@@ -232,7 +233,7 @@ ABI_SYMBOLS = [
     "PogsAmdIterate", "PogsAmdSetWarmStart", "PogsAmdGetStats", "PogsAmdResetStats", "PogsAmdDestroy", "PogsAmdLastError",
     "PogsAmdPoolStats", "PogsAmdPoolTrim",
     "PogsAmdProxEval", "PogsAmdFuncEval", "PogsAmdProjSubgradEval", "PogsAmdGetEquil", "PogsAmdProject", "PogsAmdMul", "PogsAmdRandUniform",
-    "PogsAmdReadBandwidth", "PogsAmdWaveSumCheck", "PogsAmdBatchRowsCheck", "PogsAmdBatchColsCheck",
+    "PogsAmdReadBandwidth", "PogsAmdWaveSumCheck", "PogsAmdBlockIdCheck", "PogsAmdBatchRowsCheck", "PogsAmdBatchColsCheck",
     "PogsAmdSpBatchSpmvCheck", "PogsAmdManySetupCheck", "PogsAmdGramCheck", "PogsAmdCholCheck",
     "PogsAmdSpmvCheck", "PogsAmdGetFactor",
 ]
@@ -256,6 +257,16 @@ def wave_sum_check(values):
     if lib.PogsAmdWaveSumCheck(0 if v.dtype == np.float32 else 1, v.size, v.ctypes.data, a.ctypes.data, b.ctypes.data) != 0:
         raise RuntimeError(last_error())
     return a, b
+
+
+def block_id_check(grid):
+    """(ids, group): the logical workgroup id each of `grid` blocks computes in the dense one-pass kernels, and the
+    number of index residues that are grouped (include/pogs_amd.h: PogsAmdBlockIdCheck)."""
+    import numpy as np
+    ids, group = np.empty(grid, dtype=np.int32), c_int(0)
+    if lib.PogsAmdBlockIdCheck(grid, ids.ctypes.data, ctypes.byref(group)) != 0:
+        raise RuntimeError(last_error())
+    return ids, group.value
 
 
 def _dtype_code(*arrays):

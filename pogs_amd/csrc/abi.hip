@@ -229,6 +229,11 @@ void prox_eval_host(size_t n, const int *h, const void *a, const void *b, const 
   POGS_HIP_CHECK(hipStreamSynchronize(s));
 }
 
+// the one-pass kernels' logical workgroup id of every block of a launch (PogsAmdBlockIdCheck)
+__global__ void __launch_bounds__(64) block_id_check_kernel(int *ids) {
+  if (threadIdx.x == 0) ids[blockIdx.x] = dev::logical_block_id();
+}
+
 }  // namespace
 }  // namespace pogs_amd
 
@@ -631,6 +636,18 @@ int PogsAmdWaveSumCheck(int dtype, size_t n, const void *in_host, void *alu_host
     POGS_CHECK(in_host && alu_host && lds_host, "null argument");
     if (dtype == POGS_AMD_F32) wave_sum_check(static_cast<const float *>(in_host), n, static_cast<float *>(alu_host), static_cast<float *>(lds_host));
     else wave_sum_check(static_cast<const double *>(in_host), n, static_cast<double *>(alu_host), static_cast<double *>(lds_host));
+    return 0;
+  });
+}
+
+int PogsAmdBlockIdCheck(int grid, int *ids_host, int *group) {
+  return guarded([&]() {
+    POGS_CHECK(grid > 0 && ids_host && group, "null argument / empty grid");
+    DevBuf<int> ids(static_cast<size_t>(grid));
+    hipLaunchKernelGGL(block_id_check_kernel, dim3(grid), dim3(64), 0, nullptr, ids.p);
+    POGS_HIP_CHECK(hipGetLastError());
+    POGS_HIP_CHECK(hipMemcpy(ids_host, ids.p, static_cast<size_t>(grid) * sizeof(int), hipMemcpyDeviceToHost));
+    *group = POGS_XCD_IDS ? kXcdHint : 0;
     return 0;
   });
 }

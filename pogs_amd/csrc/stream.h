@@ -644,6 +644,32 @@ struct StreamArgs2 {
   double *scalar_partials;   // [gridDim.x][Op::NS]
 };
 
+// Logical workgroup id of the one-pass kernels (ND > 0): a bijection of [0, gridDim.x) under which the workgroups
+// that share an XCD own a contiguous range of ids.  Rows, the column-partial slot and the scalar-partial slot all go
+// by the logical id, so every sum sees the same numbers in the same order as with blockIdx.x: only the physical
+// placement changes.  Rows are dealt round-robin, so the 16 floats of a 64-byte line of a y-vector belong to 16
+// consecutive ids: behind ONE L2 they merge there into a whole line, where blockIdx.x spread them over all eight
+// (the L2s are not coherent with each other: eight partly written lines per line).
+// kXcdHint is a LOCALITY HINT only -- the hardware is observed to deal blocks round-robin over its 8 XCDs, HIP promises
+// nothing (guides: MI355X_MICROARCH.md, "Workgroup dispatch, XCD placement") -- and the id is a bijection for any value
+// of it and any grid, so correctness does not depend on it.
+#ifndef POGS_XCD_IDS    // (0: blockIdx.x, as before -- A / B builds)
+#define POGS_XCD_IDS 1
+#endif
+constexpr int kXcdHint = 8;
+namespace dev {
+// (unsigned like blockIdx.x, so that with the switch off the kernels are instruction for instruction what they were)
+__device__ __forceinline__ unsigned logical_block_id() {
+#if POGS_XCD_IDS
+  const unsigned b = blockIdx.x, g = gridDim.x, x = b % kXcdHint, rem = g % kXcdHint;
+  // blocks b' < g with b' % kXcdHint < x, then this block's rank among those of its own residue
+  return x * (g / kXcdHint) + (x < rem ? x : rem) + b / kXcdHint;
+#else
+  return blockIdx.x;
+#endif
+}
+}  // namespace dev
+
 // (Measured and not kept: requesting the NEXT row tile before the current one is reduced, so that
 // the memory pipe does not idle through a slow row functor -- the logistic prox, one lane per row,
 // 0.35 us per step.  At the C3 shape the R * NV extra vector registers take the kernel from three
@@ -664,6 +690,8 @@ __global__ void __launch_bounds__(TPB, (ND > 0 ? stream2_waves_per_simd(TPB, NV,
   __shared__ T s_part[2 * R * NDD * NW];
   __shared__ T s_u[2 * R * NA];
   __shared__ double s_red[NS * NW];
+  // (the column-sum-only form has no row outputs and keeps blockIdx.x)
+  const unsigned bid = ND > 0 ? dev::logical_block_id() : blockIdx.x;
   // the second dot vector lives in LDS (dynamic, n_pad elements): it is re-read per
   // row with conflict-free 16-byte reads and frees 4*NV VGPRs for a second resident wave
   extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];
@@ -691,7 +719,7 @@ __global__ void __launch_bounds__(TPB, (ND > 0 ? stream2_waves_per_simd(TPB, NV,
 
   const int nblk = (a.m + R - 1) / R;
   int slot = 0;
-  for (int blk = blockIdx.x; blk < nblk; blk += gridDim.x, slot ^= 1) {
+  for (int blk = bid; blk < nblk; blk += gridDim.x, slot ^= 1) {
     const int row0 = blk * R;
     V av[R][NV];
 #pragma unroll
@@ -770,7 +798,7 @@ __global__ void __launch_bounds__(TPB, (ND > 0 ? stream2_waves_per_simd(TPB, NV,
   }
 #pragma unroll
   for (int q = 0; q < NA; ++q) {
-    T *out = (q == 0 ? a.col_partials0 : a.col_partials1) + static_cast<size_t>(blockIdx.x) * a.n_pad;
+    T *out = (q == 0 ? a.col_partials0 : a.col_partials1) + static_cast<size_t>(bid) * a.n_pad;
 #pragma unroll
     for (int v = 0; v < NV; ++v) {
       const int col = (v * TPB + t) * VEC;
@@ -782,7 +810,7 @@ __global__ void __launch_bounds__(TPB, (ND > 0 ? stream2_waves_per_simd(TPB, NV,
     dev::block_sum<NS, TPB>(sacc, s_red);
     if (t == 0) {
 #pragma unroll
-      for (int k = 0; k < NS; ++k) a.scalar_partials[static_cast<size_t>(blockIdx.x) * NS + k] = sacc[k];
+      for (int k = 0; k < NS; ++k) a.scalar_partials[static_cast<size_t>(bid) * NS + k] = sacc[k];
     }
   }
 }
@@ -822,6 +850,7 @@ __global__ void __launch_bounds__(TPB, (2 * (TPB / 64) + 3) / 4) stream_rows2_pf
   __shared__ T s_part[2 * R * ND * NW];
   __shared__ T s_u[2 * R * NA];
   __shared__ double s_red[NS * NW];
+  const unsigned bid = dev::logical_block_id();
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
 
   V xv[NV], x1v[NV];
@@ -844,7 +873,7 @@ __global__ void __launch_bounds__(TPB, (2 * (TPB / 64) + 3) / 4) stream_rows2_pf
   for (int k = 0; k < NS; ++k) sacc[k] = 0.0;
 
   const int nblk = (a.m + R - 1) / R;
-  int blk = blockIdx.x;
+  int blk = bid;
   V cur[R][NV];
   Pre pre_cur;
   if (t < R && blk < nblk && blk * R + t < a.m) pre_cur = op.prefetch(blk * R + t);
@@ -925,7 +954,7 @@ __global__ void __launch_bounds__(TPB, (2 * (TPB / 64) + 3) / 4) stream_rows2_pf
   }
 #pragma unroll
   for (int q = 0; q < NA; ++q) {
-    T *out = (q == 0 ? a.col_partials0 : a.col_partials1) + static_cast<size_t>(blockIdx.x) * a.n_pad;
+    T *out = (q == 0 ? a.col_partials0 : a.col_partials1) + static_cast<size_t>(bid) * a.n_pad;
 #pragma unroll
     for (int v = 0; v < NV; ++v) {
       const int col = (v * TPB + t) * VEC;
@@ -937,7 +966,7 @@ __global__ void __launch_bounds__(TPB, (2 * (TPB / 64) + 3) / 4) stream_rows2_pf
     dev::block_sum<NS, TPB>(sacc, s_red);
     if (t == 0) {
 #pragma unroll
-      for (int k = 0; k < NS; ++k) a.scalar_partials[static_cast<size_t>(blockIdx.x) * NS + k] = sacc[k];
+      for (int k = 0; k < NS; ++k) a.scalar_partials[static_cast<size_t>(bid) * NS + k] = sacc[k];
     }
   }
 }
