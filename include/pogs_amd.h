@@ -505,6 +505,36 @@ int PogsAmdSpmvCheck(int dtype, enum ORD ord, int nrows, int ncols, const int *p
                      int num_cu, int format, int force_rr_rows, int force_ncg, double scale, char trans, int sq,
                      double x_nrm2, double alpha, double beta, const void *x, size_t xlen, void *y, size_t ylen,
                      double *sumsq, int *info, int *t_ptr, int *t_ind, void *t_val);
+/* Diagnostic of the sparse solver's projection: one run of its CGLS loop on given vectors, on a live sparse handle (one
+ * GPU), by the member functions and launches an ADMM iteration uses, without the prox step.  HOST arrays of the handle's
+ * type; n-sized: x0, x_warm, x_prev, x12, x, xtemp, p, sv; m-sized: y0, y_warm, y12, y_new, ytemp, r.  A is the handle's
+ * equilibrated matrix (PogsAmdGetEquil).  The projection of (x0, y0) onto {y = A x} is started from x_warm, and y_warm
+ * stands for A x_warm (inside a solve: the previous iterate, whose y is also the y_prev of the bookkeeping, so y_warm is
+ * both here).  The entry uploads x0 / y0 into the solver's xtemp / ytemp, y_warm, x_prev, x12 and y12 into the previous
+ * iterate and the prox point, and then, by `loop`:
+ *   0  the device-resident loop (csrc/cg_fused.h): r = y0 - y_warm and x = x_warm - x0 as the prox launch leaves them,
+ *      the done flag and the step count cleared, then the loop with `ahead` (>= 1) steps enqueued before the first host
+ *      poll, at most max_steps (>= 1; a solve: 500) steps in all, the closing launch (x += x0, the sums of
+ *      (x_prev - x)^2, (x12 - x)^2, xtemp -= x, and the same of the y half from the recurrence y_warm + sum alpha q);
+ *      ysync = 1: y_new = A x by the product instead, with the y half's bookkeeping in that launch.
+ *   1  the host-polled loop (cgls_project) warm-started with x_warm and A x_warm = y_warm, then y_new = A x with the
+ *      y half's bookkeeping and the x half's launch; 2: the same loop as PogsAmdProject runs it, from x = x_warm with
+ *      both products of the start taken (y_warm only serves as y_prev).  max_steps, ahead and ysync are not used.
+ * tol: the relative tolerance of cgls.h:301-305.  Outputs: x, y_new; xtemp, ytemp as the closing launches leave them; the
+ * loop's r, p, s (sv); slots (17 doubles): the scalar block's kFcDone, kFcSteps, kFcNorms0, kFcGamma0, kFcGamma1,
+ * kFcAlpha, kFcBeta, kFcDelta, kFcIndef (loop 0 only; csrc/vec_kernels.h), kCgQ2, kCgP2, kCgS2, kCgX2 (the last step's
+ * |q|^2, |p|^2 before it, |s|^2, |x|^2), kDXprev2, kDX12, kDYprev2, kDY12; rec_x (512 doubles, loop 0): the per-block
+ * |x|^2 records of the last step, set to NaN before the loop, so that a record no block wrote comes back as NaN (the
+ * first ceil(n / 1024) are written); info (16 ints): the geometry words of PogsAmdSpmvCheck for A and A^T; *enqueued:
+ * the steps the host enqueued (loop 0) or ran (1, 2).
+ * POGS_ERROR, before any device work: a null argument, ahead < 1, max_steps < 1, loop or ysync out of range, a dense or
+ * row-sharded handle, and with loop 0 a handle whose copies are not both tiled or that was created with POGS_AMD_CG=h.
+ * The handle solves afterwards as if the call had not been made (its step prediction and its statistics are put back);
+ * a run begun with PogsAmdBeginRun is lost, PogsAmdIterate is refused until the next PogsAmdBeginRun / PogsAmdSolve. */
+int PogsAmdSparseCgCheck(PogsAmdSolver *s, const void *x0, const void *y0, const void *x_warm, const void *y_warm,
+                         const void *x_prev, const void *x12, const void *y12, double tol, int max_steps, int ahead,
+                         int ysync, int loop, void *x, void *y_new, void *xtemp, void *ytemp, void *r, void *p, void *sv,
+                         double *slots, double *rec_x, int *info, int *enqueued);
 /* W = L^-1 and U = W^T of a dense handle with the direct projector, L L^T = I + A_eq^T A_eq (m > n) or
  * I + A_eq A_eq^T: HOST outputs of k x k, k = min(m, n), either may be NULL.  On row shards every rank holds the
  * factor of the whole matrix.  POGS_ERROR on a sparse handle and on one that runs the CGLS projector. */

@@ -189,11 +189,15 @@ lib.PogsAmdCholCheck.argtypes = [c_int, c_int, c_void_p, c_size_t, c_void_p, c_v
 lib.PogsAmdSpmvCheck.argtypes = [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                  c_double, c_char, c_int, c_double, c_double, c_double, c_void_p, c_size_t, c_void_p,
                                  c_size_t, ctypes.POINTER(c_double), c_void_p, c_void_p, c_void_p, c_void_p]
+lib.PogsAmdSparseCgCheck.argtypes = [c_void_p] + [c_void_p] * 7 + [c_double, c_int, c_int, c_int, c_int] + [c_void_p] * 11
 lib.PogsAmdGetFactor.argtypes = [c_void_p, c_void_p, c_void_p]
 GRAM_AUTO, GRAM_NATIVE, GRAM_TILE_128, GRAM_TILE_256 = 0, 1, 128, 256   # `force` of PogsAmdGramCheck
 GRAM_INFO = ("path", "tile", "ksplit", "kchunk", "kacc", "units", "unit_rows", "tile_map")
 SPMV_AUTO, SPMV_TAGS, SPMV_TWO, SPMV_PLAIN = 0, 1, 2, 3   # `format` of PogsAmdSpmvCheck
 SPMV_INFO = ("tiled", "two", "rr_rows", "nrr", "ncb", "ncg", "units", "why")
+CG_FUSED, CG_HOST_WARM, CG_HOST_COLD = 0, 1, 2   # `loop` of PogsAmdSparseCgCheck
+CG_SLOTS = ("done", "steps", "norms0", "gamma0", "gamma1", "alpha", "beta", "delta", "indef", "q2", "p2", "s2", "x2",
+            "dxprev2", "dx12", "dyprev2", "dy12")
 # `why` of a copy that is not tiled
 SPMV_WHY = {0: "tiled", 1: "no non-zeros", 2: "plan too large", 3: "planner range", 4: "padding", 5: "row count over 16 bits",
             6: "pinned plain"}
@@ -235,7 +239,7 @@ ABI_SYMBOLS = [
     "PogsAmdProxEval", "PogsAmdFuncEval", "PogsAmdProjSubgradEval", "PogsAmdGetEquil", "PogsAmdProject", "PogsAmdMul", "PogsAmdRandUniform",
     "PogsAmdReadBandwidth", "PogsAmdWaveSumCheck", "PogsAmdBlockIdCheck", "PogsAmdBatchRowsCheck", "PogsAmdBatchColsCheck",
     "PogsAmdSpBatchSpmvCheck", "PogsAmdManySetupCheck", "PogsAmdGramCheck", "PogsAmdCholCheck",
-    "PogsAmdSpmvCheck", "PogsAmdGetFactor",
+    "PogsAmdSpmvCheck", "PogsAmdSparseCgCheck", "PogsAmdGetFactor",
 ]
 
 
@@ -425,6 +429,35 @@ def spmv_check(ptr, ind, val, shape, x, y, trans="n", ord=ROW_MAJ, num_cu=0, for
     if t is None:
         return y, sumsq.value, infos
     return y, sumsq.value, infos, (t[0], t[1][:nnz], t[2][:nnz])
+
+
+def sparse_cg_check(handle, x0, y0, x_warm, y_warm, x_prev, x12, y12, tol, max_steps=500, ahead=1, ysync=False,
+                    loop=CG_FUSED):
+    """One projection of a live sparse handle's CGLS loop on given vectors (include/pogs_amd.h: PogsAmdSparseCgCheck).
+    Vectors of the handle's dtype: x0, x_warm, x_prev, x12 of one length (n), y0, y_warm, y12 of another (m).  Returns a
+    dict: x, y_new, xtemp, ytemp, r, p, s (arrays), the scalars of CG_SLOTS (floats), rec_x (the 512 |x|^2 records), info = (info_A, info_At) as
+    spmv_check gives them, and enqueued."""
+    import numpy as np
+    xs = [np.ascontiguousarray(v) for v in (x0, x_warm, x_prev, x12)]
+    ys = [np.ascontiguousarray(v) for v in (y0, y_warm, y12)]
+    _dtype_code(*(xs + ys))
+    if any(v.ndim != 1 or v.size != xs[0].size for v in xs) or any(v.ndim != 1 or v.size != ys[0].size for v in ys):
+        raise ValueError("x0, x_warm, x_prev, x12 of one length, y0, y_warm, y12 of another")
+    dt, n, m = xs[0].dtype, xs[0].size, ys[0].size
+    out = dict(x=np.empty(n, dt), y_new=np.empty(m, dt), xtemp=np.empty(n, dt), ytemp=np.empty(m, dt), r=np.empty(m, dt),
+               p=np.empty(n, dt), s=np.empty(n, dt))
+    slots, info, enq = np.zeros(len(CG_SLOTS), np.float64), np.zeros(16, np.int32), c_int(0)
+    out["rec_x"] = np.zeros(512, np.float64)
+    if lib.PogsAmdSparseCgCheck(handle, xs[0].ctypes.data, ys[0].ctypes.data, xs[1].ctypes.data, ys[1].ctypes.data,
+                                xs[2].ctypes.data, xs[3].ctypes.data, ys[2].ctypes.data, tol, int(max_steps), int(ahead),
+                                int(bool(ysync)), int(loop), *(out[k].ctypes.data for k in ("x", "y_new", "xtemp", "ytemp",
+                                                                                            "r", "p", "s")),
+                                slots.ctypes.data, out["rec_x"].ctypes.data, info.ctypes.data, ctypes.addressof(enq)) != 0:
+        raise RuntimeError(last_error())
+    out.update(zip(CG_SLOTS, (float(v) for v in slots)))
+    out["info"] = tuple(dict(zip(SPMV_INFO, (int(v) for v in info[8 * c:8 * c + 8]))) for c in range(2))
+    out["enqueued"] = enq.value
+    return out
 
 
 def chol_check(H, ldo=None):

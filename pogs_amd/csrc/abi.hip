@@ -746,6 +746,27 @@ int PogsAmdSpmvCheck(int dtype, enum ORD ord, int nrows, int ncols, const int *p
   });
 }
 
+int PogsAmdSparseCgCheck(PogsAmdSolver *s, const void *x0, const void *y0, const void *x_warm, const void *y_warm,
+                         const void *x_prev, const void *x12, const void *y12, double tol, int max_steps, int ahead,
+                         int ysync, int loop, void *x, void *y_new, void *xtemp, void *ytemp, void *r, void *p, void *sv,
+                         double *slots, double *rec_x, int *info, int *enqueued) {
+  return guarded([&]() {
+    // every refusal comes before the first HIP call (the handle's own: a dense one, row shards, copies not tiled)
+    POGS_CHECK(x0 && y0 && x_warm && y_warm && x_prev && x12 && y12 && x && y_new && xtemp && ytemp && r && p && sv &&
+                   slots && rec_x && info && enqueued,
+               "null argument");
+    POGS_CHECK(loop >= 0 && loop <= 2, "loop must be 0 (device-resident), 1 (host-polled, warm) or 2 (host-polled, cold)");
+    POGS_CHECK(ysync == 0 || ysync == 1, "ysync must be 0 or 1");
+    POGS_CHECK(ahead >= 1, "ahead must be >= 1");
+    POGS_CHECK(max_steps >= 1, "max_steps must be >= 1");
+    POGS_CHECK(s && s->impl, "null solver");
+    DeviceGuard guard(s->impl->device());
+    s->impl->sparse_cg_check(SparseCgCheckArgs{x0, y0, x_warm, y_warm, x_prev, x12, y12, tol, max_steps, ahead, ysync, loop,
+                                               x, y_new, xtemp, ytemp, r, p, sv, slots, rec_x, info, enqueued});
+    return 0;
+  });
+}
+
 int PogsAmdGetFactor(const PogsAmdSolver *s, void *W, void *U) {
   return guarded([&]() {
     POGS_CHECK(s && s->impl, "null solver");

@@ -679,6 +679,18 @@ struct BatchOut {
   int *status;
 };
 
+// PogsAmdSparseCgCheck (include/pogs_amd.h, Part 3): HOST arrays of the handle's type, n- or m-sized as named there
+struct SparseCgCheckArgs {
+  const void *x0, *y0, *x_warm, *y_warm, *x_prev, *x12, *y12;
+  double tol;
+  int max_steps, ahead, ysync, loop;
+  void *x, *y_new, *xtemp, *ytemp, *r, *p, *s;
+  double *slots;   // 17
+  double *rec_x;   // kCgfBlocks = 512
+  int *info;       // 16
+  int *enqueued;
+};
+
 // Type-erased solver behind the C handle.
 struct SolverBase {
   virtual ~SolverBase() {}
@@ -702,6 +714,8 @@ struct SolverBase {
   // the dense direct projector's W = L^-1 and U = W^T (HOST, k x k, either may be null)
   virtual void get_factor(void *, void *) { throw Error("PogsAmdGetFactor needs a dense handle"); }
   virtual void project(const void *x0, const void *y0, double tol, void *x, void *y) = 0;
+  // one projection of the sparse solver's CGLS loops on given vectors (one GPU)
+  virtual void sparse_cg_check(const SparseCgCheckArgs &) { throw Error("PogsAmdSparseCgCheck needs a sparse handle"); }
   virtual void mul(char trans, double alpha, const void *x, double beta, void *y) = 0;
   virtual PogsAmdStats &stats() = 0;
   // guarded() in abi.hip: on_entry() when an entry point starts working on the handle, on_error()

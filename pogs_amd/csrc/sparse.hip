@@ -176,6 +176,80 @@ class SparseSolver final : public SolverBase {
     ctx_.sync();
   }
 
+  // PogsAmdSparseCgCheck: one projection on given vectors, by cg_loop_fused (loop 0) or cgls_project (1 warm, 2 cold)
+  // with the launches iteration() puts around it, minus the prox step
+  void sparse_cg_check(const SparseCgCheckArgs &a) override {
+    POGS_CHECK(!multi_, "PogsAmdSparseCgCheck: a row-sharded handle is not supported");
+    if (a.loop == 0) {
+      POGS_CHECK(op_->A().sell_ready && op_->At().sell_ready,
+                 "PogsAmdSparseCgCheck: the device-resident loop needs both copies tiled");
+      POGS_CHECK(fused_cg_, "PogsAmdSparseCgCheck: the handle does not run the device-resident loop");
+    }
+    hipStream_t s = ctx_.stream;
+    ctx_.sync();
+    const PogsAmdStats stats0 = ctx_.stats;
+    const int pred0 = cg_pred_;
+    const unsigned long long timed0 = timed_spmvs_;
+    double *S = ctx_.S.p;
+    const int nw = cur_ ^ 1;
+    T *x = x_[nw].p, *xw = xout_.p;   // (xout_: free between solves)
+    double *rec_x = ctx_.spart.p + sp_cgx_off_;
+    auto up = [&](T *dst, const void *src, int cnt) {
+      POGS_HIP_CHECK(hipMemcpyAsync(dst, src, static_cast<size_t>(cnt) * sizeof(T), hipMemcpyHostToDevice, s));
+    };
+    auto down = [&](void *dst, const T *src, int cnt) {
+      POGS_HIP_CHECK(hipMemcpyAsync(dst, src, static_cast<size_t>(cnt) * sizeof(T), hipMemcpyDeviceToHost, s));
+    };
+    up(xtemp_.p, a.x0, n_); up(ytemp_.p, a.y0, m_); up(xw, a.x_warm, n_); up(y_[cur_].p, a.y_warm, m_);
+    up(x_[cur_].p, a.x_prev, n_); up(x12_.p, a.x12, n_); up(y12_.p, a.y12, m_);
+    int enq = 0;
+    if (a.loop == 0) {
+      // what admm_pre_kernel leaves: r = y0 - y_warm, x = x_warm - x0, the done flag and the step count cleared
+      hipLaunchKernelGGL(sub_norm_kernel<T>, dim3(vec_blocks(m_)), dim3(kVecTpb), 0, s, m_, ytemp_.p, y_[cur_].p, cg_r_.p,
+                         ctx_.spart.p);
+      hipLaunchKernelGGL(sub_norm_kernel<T>, dim3(vec_blocks(n_)), dim3(kVecTpb), 0, s, n_, xw, xtemp_.p, x, ctx_.spart.p);
+      static_assert(kFcSteps == kFcDone + 1, "slot order");
+      POGS_HIP_CHECK(hipMemsetAsync(S + kFcDone, 0, 2 * sizeof(double), s));
+      launch_fill<double>(rec_x, std::numeric_limits<double>::quiet_NaN(), kCgfBlocks, s);
+      cg_loop_fused(x, nw, a.ysync != 0, a.ahead, a.max_steps, a.tol, nullptr, &enq);
+    } else {
+      const unsigned long long cg0 = ctx_.stats.cg_iters;
+      if (a.loop == 1) {
+        cgls_project(xtemp_.p, ytemp_.p, x, static_cast<T>(a.tol), y_[cur_].p, xw);
+      } else {
+        POGS_HIP_CHECK(hipMemcpyAsync(x, xw, n_ * sizeof(T), hipMemcpyDeviceToDevice, s));
+        cgls_project(xtemp_.p, ytemp_.p, x, static_cast<T>(a.tol));
+      }
+      spmv<false>(op_->A(), x, nullptr, SpTailOp<T>{y_[nw].p, y_[cur_].p, y12_.p, ytemp_.p}, S + kDYprev2, true);
+      launch_admm_tail<T>(n_, x, x_[cur_].p, x12_.p, xtemp_.p, ctx_.spart.p, s);
+      ctx_.queue_sum(SumJob{ctx_.spart.p, vec_blocks(n_), 2, S + kDXprev2});
+      ctx_.fetch_scalars();
+      enq = static_cast<int>(ctx_.stats.cg_iters - cg0);
+    }
+    POGS_HIP_CHECK(hipGetLastError());
+    down(a.x, x, n_); down(a.y_new, y_[nw].p, m_); down(a.xtemp, xtemp_.p, n_); down(a.ytemp, ytemp_.p, m_);
+    down(a.r, cg_r_.p, m_); down(a.p, cg_p_.p, n_); down(a.s, cg_s_.p, n_);
+    double hS[kNumSlots];
+    POGS_HIP_CHECK(hipMemcpyAsync(hS, S, kNumSlots * sizeof(double), hipMemcpyDeviceToHost, s));
+    POGS_HIP_CHECK(hipMemcpyAsync(a.rec_x, rec_x, kCgfBlocks * sizeof(double), hipMemcpyDeviceToHost, s));
+    ctx_.sync();
+    int k = 0;
+    for (int slot = kFcDone; slot <= kFcIndef; ++slot) a.slots[k++] = hS[slot];
+    for (int slot : {kCgQ2, kCgP2, kCgS2, kCgX2, kDXprev2, kDX12, kDYprev2, kDY12}) a.slots[k++] = hS[slot];
+    for (int c = 0; c < 2; ++c) op_->describe(c, a.info + 8 * c);
+    *a.enqueued = enq;
+    // the handle as it was, for the next solve: the prediction, the counters, no timed launch kept; the vectors of a
+    // run in progress (PogsAmdBeginRun / PogsAmdIterate) are gone
+    ctx_.stats = stats0;
+    cg_pred_ = pred0;
+    timed_spmvs_ = timed0;
+    if (ctx_.stream_timer.enabled()) {
+      unsigned long long cnt = 0;
+      (void)ctx_.stream_timer.collect_ms(&cnt);
+    }
+    loaded_ = false;
+  }
+
   void mul(char trans, double alpha, const void *x, double beta, void *y) override {
     hipStream_t s = ctx_.stream;
     const bool tr = (trans == 't' || trans == 'T');
@@ -519,14 +593,6 @@ class SparseSolver final : public SolverBase {
   // The prox step and the projection of one iteration with the device-resident CGLS loop
   // (cg_fused.h): 6 launches per CG step, one host poll.  Returns the published block.
   const double *prox_and_project_fused(const AdmmPreArgs<T> &pa0, int nw) {
-    hipStream_t s = ctx_.stream;
-    const int bx = pre_blocks(n_), bm = pre_blocks(m_);
-    double *S = ctx_.S.p;
-    double *rec_t = cg_rec_.p, *rec_a = cg_rec_.p + cg_rec_cap_;          // A^T products, A products
-    double *rec_x = ctx_.spart.p + sp_cgx_off_, *rec_p = ctx_.spart.p + sp_cgp_off_;
-    double *cpart = ctx_.spart.p;   // closing launch: [bx + bm][2]
-    const double shift = 1.0, kEps = std::numeric_limits<T>::epsilon();
-    const double tol = static_cast<double>(ctl_.proj_tol());
     T *x = x_[nw].p;
     // y = A x by the recurrence, except every ysync_-th projection (and the first), which takes the
     // product itself
@@ -537,8 +603,26 @@ class SparseSolver final : public SolverBase {
     AdmmPreArgs<T> pa = pa0;
     pa.x_aux = x;
     pa.y_aux = cg_r_.p;
-    pa.cg_reset = S + kFcDone;
-    launch_admm_pre<T>(pa, s);
+    pa.cg_reset = ctx_.S.p + kFcDone;
+    launch_admm_pre<T>(pa, ctx_.stream);
+    // at most 500 steps (projector_cgls.cpp:17), as many as the previous projection took enqueued ahead
+    return cg_loop_fused(x, nw, ysync, cg_pred_, 500, static_cast<double>(ctl_.proj_tol()), pa.partials);
+  }
+
+  // The loop proper: on entry x = x_warm - x0 (x: x_[nw]), cg_r_ = y0 - A x_warm, xtemp_ / ytemp_ = x0 / y0, x_[cur_] /
+  // y_[cur_] the previous iterate (y_[cur_] = A x_warm starts the y recurrence) and S[kFcDone] = S[kFcSteps] = 0.
+  // `ahead_steps` steps are enqueued before the first poll, at most `max_steps` in all.  pre_part: the prox step's partial
+  // sums, summed with the closing launch's (null, one GPU only: there was no prox step -- sparse_cg_check).
+  // *enqueued (optional): the steps the host enqueued.
+  const double *cg_loop_fused(T *x, int nw, bool ysync, int ahead_steps, int max_steps, double tol, double *pre_part,
+                              int *enqueued = nullptr) {
+    hipStream_t s = ctx_.stream;
+    const int bx = pre_blocks(n_), bm = pre_blocks(m_);
+    double *S = ctx_.S.p;
+    double *rec_t = cg_rec_.p, *rec_a = cg_rec_.p + cg_rec_cap_;          // A^T products, A products
+    double *rec_x = ctx_.spart.p + sp_cgx_off_, *rec_p = ctx_.spart.p + sp_cgp_off_;
+    double *cpart = ctx_.spart.p;   // closing launch: [bx + bm][2]
+    const double shift = 1.0, kEps = std::numeric_limits<T>::epsilon();
     std::vector<size_t> &ev = fused_events_;
     ev.clear();
     size_t e;
@@ -609,7 +693,7 @@ class SparseSolver final : public SolverBase {
       b.n = n_; b.S = S; b.k = enq;
       b.rec_s = rec_s2; b.nrec_s = nrec_s;
       b.rec_x = rec_x; b.nrec_x = gp;
-      b.tol = tol; b.maxit = 500;                                             // projector_cgls.cpp:17
+      b.tol = tol; b.maxit = max_steps;
       b.s = cg_s_.p; b.p = cg_p_.p; b.rec_p = rec_p;
       hipLaunchKernelGGL(cgf_step_b_kernel<T>, dim3(gp), dim3(kCgfTpb), 0, s, b);
       ++enq;
@@ -623,27 +707,27 @@ class SparseSolver final : public SolverBase {
       c.ynew = ysync ? nullptr : y_[nw].p; c.yprev = y_[cur_].p; c.y12 = y12_.p; c.ytemp = ytemp_.p;
       c.part = cpart; c.blocks_x = bx;
       hipLaunchKernelGGL(cgf_close_kernel<T>, dim3(ysync ? bx : bx + bm), dim3(kVecTpb), 0, s, c);
-      ctx_.queue_sum(SumJob{pa.partials, bx, 3, S + kGapX});
+      if (pre_part) ctx_.queue_sum(SumJob{pre_part, bx, 3, S + kGapX});
       ctx_.queue_sum(SumJob{cpart, bx, 2, S + kDXprev2});
       if (!multi_) {
-        ctx_.queue_sum(SumJob{pa.partials + static_cast<size_t>(bx) * 3, bm, 3, S + kGapY});
+        if (pre_part) ctx_.queue_sum(SumJob{pre_part + static_cast<size_t>(bx) * 3, bm, 3, S + kGapY});
         if (!ysync) ctx_.queue_sum(SumJob{cpart + static_cast<size_t>(bx) * 2, bm, 2, S + kDYprev2});
       } else {
         // the y-side sums are over this rank's rows: slots kGapY .. kDY12 are adjacent, one all-reduce
         static_assert(kWY2 == kGapY + 1 && kHY2 == kGapY + 2 && kDYprev2 == kGapY + 3 && kDY12 == kGapY + 4, "slot order");
-        SumJob j[2] = {{pa.partials + static_cast<size_t>(bx) * 3, bm, 3, S + kGapY},
+        SumJob j[2] = {{pre_part + static_cast<size_t>(bx) * 3, bm, 3, S + kGapY},
                        {cpart + static_cast<size_t>(bx) * 2, bm, 2, S + kDYprev2}};
         launch_sum_jobs(j, ysync ? 1 : 2, s);
         ctx_.dist.allreduce(S + kGapY, ysync ? 3 : 5, s);
       }
       return ctx_.fetch_scalars();
     };
-    const int ahead = std::max(1, std::min(cg_pred_, 500));
+    const int ahead = std::max(1, std::min(ahead_steps, max_steps));
     for (int k = 0; k < ahead; ++k) step();
     const double *Sh = close();
     int more = 1;
     while (Sh[kFcDone] == 0.0) {   // the loop needed more steps than the previous projection
-      for (int k = 0; k < more && enq < 500; ++k) step();
+      for (int k = 0; k < more && enq < max_steps; ++k) step();
       Sh = close();
       more = std::min(2 * more, 64);   // a growing chunk per host poll, not one step per poll
     }
@@ -659,6 +743,7 @@ class SparseSolver final : public SolverBase {
       reduce_y_scalars(S + kDYprev2, 2);
       Sh = ctx_.fetch_scalars();
     }
+    if (enqueued) *enqueued = enq;
     return Sh;
   }
 

@@ -162,3 +162,27 @@ def test_a_null_coefficient_array_is_refused_by_the_array_entry_points(capfd):
         msg = _lib.last_error()
         assert "null coefficient array" in msg and "description of %s" % which in msg, msg
     capfd.readouterr()
+
+
+def test_sparse_cg_check_refuses_bad_arguments_before_any_gpu_work():
+    """PogsAmdSparseCgCheck (Part 3) checks its own arguments before it looks at the handle, and the handle before any
+    device call: POGS_ERROR and a message that names the argument, without a GPU."""
+    import numpy as np
+
+    n, m = 4, 6
+    ins = [np.zeros(k, np.float32) for k in (n, m, n, m, n, n, m)]
+    outs = [np.zeros(k, np.float32) for k in (n, m, n, m, m, n, n)] + [np.zeros(17), np.zeros(512), np.zeros(16, np.int32),
+                                                                       np.zeros(1, np.int32)]
+    ptrs = [a.ctypes.data for a in ins + outs]
+
+    def call(null=None, tol=1e-3, max_steps=500, ahead=1, ysync=0, loop=0):
+        p = list(ptrs)
+        if null is not None:
+            p[null] = None
+        rc = _lib.lib.PogsAmdSparseCgCheck(None, *p[:7], tol, max_steps, ahead, ysync, loop, *p[7:])
+        return rc, _lib.last_error()
+
+    for kw, word in ((dict(ahead=0), "ahead"), (dict(max_steps=0), "max_steps"), (dict(loop=3), "loop"), (dict(loop=-1), "loop"),
+                     (dict(ysync=2), "ysync"), (dict(), "null solver")) + tuple((dict(null=i), "null argument") for i in range(18)):
+        rc, msg = call(**kw)
+        assert rc == 6 and word in msg, (kw, rc, msg)
