@@ -102,8 +102,11 @@ typedef struct PogsAmdSolver PogsAmdSolver; /* opaque */
 
 enum POGS_AMD_DTYPE { POGS_AMD_F32 = 0, POGS_AMD_F64 = 1 };
 enum POGS_AMD_MEM { POGS_AMD_HOST = 0, POGS_AMD_DEVICE = 1 };
-enum POGS_AMD_PROJECTOR { POGS_AMD_PROJ_DEFAULT = 0, /* dense: direct, sparse: CGLS */
+enum POGS_AMD_PROJECTOR { POGS_AMD_PROJ_DEFAULT = 0, /* dense: direct; sparse: CGLS by default, DIRECT for
+                                                        min(m, n) <= POGS_AMD_SPARSE_DIRECT_MAX, one GPU */
                           POGS_AMD_PROJ_DIRECT = 1, POGS_AMD_PROJ_CGLS = 2 };
+/* largest min(m, n) of a sparse handle with the direct projector (its factor is two dense K x K matrices) */
+#define POGS_AMD_SPARSE_DIRECT_MAX 16384
 
 #define POGS_AMD_UNIQUE_ID_BYTES 128
 
@@ -178,7 +181,14 @@ int PogsAmdCreateDense(PogsAmdSolver **out, int dtype, enum ORD ord, size_t m,
 /* Create a solver for a sparse matrix (CSR if ord == ROW_MAJ, else CSC);
  * data/ptr/ind are host or device pointers (mem).  With dist (may be NULL) the
  * matrix is this rank's block of m consecutive rows, given as CSR (SURVEY.md
- * section 8 f.3): CGLS with the A^T products and row sums all-reduced. */
+ * section 8 f.3): CGLS with the A^T products and row sums all-reduced.
+ * opt->projector: DEFAULT and CGLS run CGLS.  DIRECT (single GPU, min(m, n) <= POGS_AMD_SPARSE_DIRECT_MAX) forms
+ * I + A_eq^T A_eq (m > n) or I + A_eq A_eq^T from the sparse copies after the equilibration, factors and inverts it
+ * as a dense handle does and keeps W = L^-1 and U = W^T (2 K^2 elements, K = min(m, n)): every projection is then
+ * two products with A / A^T and two triangular mat-vecs, exact, with no inner loop (stats: cg_iters stays 0, matvecs
+ * counts 2 products per iteration and 2 more on an iteration with exact residuals; gram_ms, chol_ms, trtri_ms the
+ * set-up).  DIRECT with a larger short side or with dist is refused before anything is built: POGS_ERROR, *out NULL,
+ * PogsAmdLastError says why. */
 int PogsAmdCreateSparse(PogsAmdSolver **out, int dtype, enum ORD ord, size_t m,
                         size_t n, size_t nnz, const void *data, const int *ptr,
                         const int *ind, int mem, const PogsAmdOptions *opt,
@@ -235,7 +245,9 @@ int PogsAmdSolveBatchFn(PogsAmdSolver *s, int k, const PogsAmdFn *f, const PogsA
  * device memory.  Every product with A or A^T reads the equilibrated matrix once for all active problems.  The
  * projection is a batched CGLS: each problem runs its own CG (shift 1, at most 500 steps, its own tolerance,
  * warm-started from its previous x) and leaves the product's slot list when its CG stops.  A problem's outputs do not
- * depend on k, on its position or on the other problems.  Stats: `iterations` batch iterations, `matvecs`
+ * depend on k, on its position or on the other problems.  On a handle with the direct projector the projection is
+ * exact instead -- two shared products and the two triangular row passes over W and U, no inner loop and no host poll
+ * inside it -- `cg_iters` is 0, and the same independence holds.  Stats: `iterations` batch iterations, `matvecs`
  * multi-vector products, `cg_iters` batched CG steps, reserved[4] problem-iterations, reserved[5..7] with
  * options.profile the products' HIP-event time (ms), launch count and algorithmic bytes.
  * Returns 0 when the batch ran (status[j] holds each PogsStatus), POGS_ERROR when refused (PogsAmdLastError says
@@ -393,7 +405,8 @@ int PogsAmdProjSubgradEval(int dtype, size_t n, const int *h, const void *a, con
 /* Equilibrated matrix, scalings and norm estimate of a solver (HOST outputs,
  * any may be NULL): A_eq (m*n row-major), d (m), e (n). */
 int PogsAmdGetEquil(const PogsAmdSolver *s, void *A_eq, void *d, void *e, double *nrmA);
-/* Projection onto {y = A_eq x}: (x, y) = argmin |x-x0|^2 + |y-y0|^2 (HOST ptrs). */
+/* Projection onto {y = A_eq x}: (x, y) = argmin |x-x0|^2 + |y-y0|^2 (HOST ptrs).  tol: the relative tolerance of
+ * a CGLS handle's loop; a handle with the direct projector (dense or sparse) projects exactly and ignores it. */
 int PogsAmdProject(PogsAmdSolver *s, const void *x0, const void *y0, double tol,
                    void *x, void *y);
 /* y = alpha * op(A_eq) x + beta * y on the solver's operator (HOST ptrs);
@@ -528,17 +541,35 @@ int PogsAmdSpmvCheck(int dtype, enum ORD ord, int nrows, int ncols, const int *p
  * first ceil(n / 1024) are written); info (16 ints): the geometry words of PogsAmdSpmvCheck for A and A^T; *enqueued:
  * the steps the host enqueued (loop 0) or ran (1, 2).
  * POGS_ERROR, before any device work: a null argument, ahead < 1, max_steps < 1, loop or ysync out of range, a dense or
- * row-sharded handle, and with loop 0 a handle whose copies are not both tiled or that was created with POGS_AMD_CG=h.
+ * row-sharded handle, a sparse handle with the direct projector (it has no CGLS loop), and with loop 0 a handle whose copies are not both tiled or that was created with POGS_AMD_CG=h.
  * The handle solves afterwards as if the call had not been made (its step prediction and its statistics are put back);
  * a run begun with PogsAmdBeginRun is lost, PogsAmdIterate is refused until the next PogsAmdBeginRun / PogsAmdSolve. */
 int PogsAmdSparseCgCheck(PogsAmdSolver *s, const void *x0, const void *y0, const void *x_warm, const void *y_warm,
                          const void *x_prev, const void *x12, const void *y12, double tol, int max_steps, int ahead,
                          int ysync, int loop, void *x, void *y_new, void *xtemp, void *ytemp, void *r, void *p, void *sv,
                          double *slots, double *rec_x, int *info, int *enqueued);
-/* W = L^-1 and U = W^T of a dense handle with the direct projector, L L^T = I + A_eq^T A_eq (m > n) or
- * I + A_eq A_eq^T: HOST outputs of k x k, k = min(m, n), either may be NULL.  On row shards every rank holds the
- * factor of the whole matrix.  POGS_ERROR on a sparse handle and on one that runs the CGLS projector. */
+/* W = L^-1 and U = W^T of a handle with the direct projector (dense, or sparse created with POGS_AMD_PROJ_DIRECT),
+ * L L^T = I + A_eq^T A_eq (m > n) or I + A_eq A_eq^T: HOST outputs of k x k, k = min(m, n), either may be NULL.  On
+ * row shards every rank holds the factor of the whole matrix.  POGS_ERROR on a handle that runs the CGLS projector
+ * (a sparse one: "needs a dense handle"). */
 int PogsAmdGetFactor(const PogsAmdSolver *s, void *W, void *U);
+/* Diagnostics of the sparse direct projector (csrc/sparse_direct.h).  HOST arrays of type dtype; invalid arguments are
+ * refused before any device work, as above. */
+/* The lower triangle of the Gram matrix a direct sparse handle factors, G = A^T A (nrows > ncols, K = ncols) or A A^T
+ * (K = nrows), by the launch its set-up runs, on copies built as a handle builds them (the matrix as PogsAmdSpmvCheck
+ * takes it: CSR or CSC, indices unsorted and entries repeated allowed, no empty matrix; the values are used as given,
+ * without equilibration).  Sums are formed in double for both types and rounded once; the result depends on the
+ * matrix alone (not on window, num_cu or the run).  K <= POGS_AMD_SPARSE_DIRECT_MAX.  num_cu: 0 = the device's.
+ * window: the columns of a row a wavefront accumulates in LDS at a time: 0 = the solver's choice, else a multiple of
+ * 64 in [64, 2048].  G: K x ldg row-major (ldg >= K), uploaded before and downloaded after: every G[i][j], j <= i, is
+ * written (zeros included), the strict upper triangle and the columns >= K come back as given.  info (8 ints) = {K,
+ * 1 if nrows > ncols, window used, windows of the last row, workgroups, leading dimension on the device, 0, 0}. */
+int PogsAmdSparseGramCheck(int dtype, enum ORD ord, int nrows, int ncols, const int *ptr, const int *ind,
+                           const void *val, int num_cu, int window, void *G, size_t ldg, int *info);
+/* y = tri(M) x by the solo solve's triangular mat-vec: M n x ldm row-major (ldm a multiple of VEC, >= n), tri 1: the
+ * lower triangle (columns 0 .. i of row i), 2: the upper one (columns i .. n - 1); x, y: n elements.  Nothing outside
+ * the triangle and nothing in columns n .. ldm is read. */
+int PogsAmdTriMatvecCheck(int dtype, int tri, int n, const void *M, size_t ldm, const void *x, void *y);
 /* The Norm2Est start vector (reference: gsl::rand, src/cpu/include/gsl/gsl_rand.h:8-16). */
 int PogsAmdRandUniform(int dtype, size_t n, void *out_host);
 

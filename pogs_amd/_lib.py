@@ -191,6 +191,12 @@ lib.PogsAmdSpmvCheck.argtypes = [c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                  c_size_t, ctypes.POINTER(c_double), c_void_p, c_void_p, c_void_p, c_void_p]
 lib.PogsAmdSparseCgCheck.argtypes = [c_void_p] + [c_void_p] * 7 + [c_double, c_int, c_int, c_int, c_int] + [c_void_p] * 11
 lib.PogsAmdGetFactor.argtypes = [c_void_p, c_void_p, c_void_p]
+lib.PogsAmdSparseGramCheck.argtypes = [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                       c_size_t, c_void_p]
+lib.PogsAmdTriMatvecCheck.argtypes = [c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p]
+SPARSE_DIRECT_MAX = 16384   # include/pogs_amd.h: POGS_AMD_SPARSE_DIRECT_MAX
+SPARSE_GRAM_INFO = ("K", "tall", "window", "windows", "grid", "ld")
+TRI_LOWER, TRI_UPPER = 1, 2   # `tri` of PogsAmdTriMatvecCheck / PogsAmdBatchRowsCheck
 GRAM_AUTO, GRAM_NATIVE, GRAM_TILE_128, GRAM_TILE_256 = 0, 1, 128, 256   # `force` of PogsAmdGramCheck
 GRAM_INFO = ("path", "tile", "ksplit", "kchunk", "kacc", "units", "unit_rows", "tile_map")
 SPMV_AUTO, SPMV_TAGS, SPMV_TWO, SPMV_PLAIN = 0, 1, 2, 3   # `format` of PogsAmdSpmvCheck
@@ -239,7 +245,7 @@ ABI_SYMBOLS = [
     "PogsAmdProxEval", "PogsAmdFuncEval", "PogsAmdProjSubgradEval", "PogsAmdGetEquil", "PogsAmdProject", "PogsAmdMul", "PogsAmdRandUniform",
     "PogsAmdReadBandwidth", "PogsAmdWaveSumCheck", "PogsAmdBlockIdCheck", "PogsAmdBatchRowsCheck", "PogsAmdBatchColsCheck",
     "PogsAmdSpBatchSpmvCheck", "PogsAmdManySetupCheck", "PogsAmdGramCheck", "PogsAmdCholCheck",
-    "PogsAmdSpmvCheck", "PogsAmdSparseCgCheck", "PogsAmdGetFactor",
+    "PogsAmdSpmvCheck", "PogsAmdSparseCgCheck", "PogsAmdGetFactor", "PogsAmdSparseGramCheck", "PogsAmdTriMatvecCheck",
 ]
 
 
@@ -477,8 +483,49 @@ def chol_check(H, ldo=None):
     return L, W, U
 
 
+def sparse_gram_check(ptr, ind, val, shape, G, ord=ROW_MAJ, window=0, num_cu=0):
+    """(G, info): the lower triangle of A^T A (nrows > ncols) or A A^T in G[:K, :K], K = min(shape), by the Gram launch
+    of a sparse handle's direct projector (include/pogs_amd.h: PogsAmdSparseGramCheck).  shape = (nrows, ncols) of A;
+    ptr / ind / val: its CSR (ord = ROW_MAJ) or CSC (COL_MAJ) arrays, used as given; G: K x ldg; window: 0 or a multiple
+    of 64 in [64, 2048]; info: dict of SPARSE_GRAM_INFO.  Returns a new array; G itself is not changed."""
+    import numpy as np
+    ptr, ind = np.ascontiguousarray(ptr, dtype=np.int32), np.ascontiguousarray(ind, dtype=np.int32)
+    val = np.ascontiguousarray(val)
+    G = np.array(G, order="C", copy=True)
+    code = _dtype_code(val, G)
+    nrows, ncols = int(shape[0]), int(shape[1])
+    r1 = nrows if ord == ROW_MAJ else ncols
+    if ptr.ndim != 1 or ptr.size != r1 + 1 or G.ndim != 2 or G.shape[0] != min(nrows, ncols) or G.shape[1] < G.shape[0]:
+        raise ValueError("ptr (rows of the given copy + 1), G (K, ldg >= K) with K = min(shape)")
+    nnz = max(int(ptr[-1]), 0)
+    if ind.size < nnz or val.size < nnz:
+        raise ValueError("ind and val must hold ptr[-1] entries")
+    info = np.zeros(8, dtype=np.int32)
+    if lib.PogsAmdSparseGramCheck(code, ord, nrows, ncols, ptr.ctypes.data, ind.ctypes.data, val.ctypes.data, num_cu,
+                                  int(window), G.ctypes.data, G.shape[1], info.ctypes.data) != 0:
+        raise RuntimeError(last_error())
+    return G, dict(zip(SPARSE_GRAM_INFO, (int(v) for v in info)))
+
+
+def tri_matvec_check(tri, M, x, y=None):
+    """y = tri(M) x by the triangular mat-vec of a sparse handle's direct projector (include/pogs_amd.h:
+    PogsAmdTriMatvecCheck).  M: n x ldm (ldm a multiple of the 16-byte vector), x: n; tri: TRI_LOWER / TRI_UPPER.  y
+    (optional, n): what the output starts as.  Returns a new array."""
+    import numpy as np
+    M, x = np.ascontiguousarray(M), np.ascontiguousarray(x)
+    if M.ndim != 2 or x.ndim != 1 or x.size != M.shape[0] or M.shape[1] < M.shape[0]:
+        raise ValueError("M (n, ldm >= n), x (n)")
+    y = np.zeros_like(x) if y is None else np.array(y, order="C", copy=True)
+    code = _dtype_code(M, x, y)
+    if y.shape != x.shape:
+        raise ValueError("y (n)")
+    if lib.PogsAmdTriMatvecCheck(code, int(tri), M.shape[0], M.ctypes.data, M.shape[1], x.ctypes.data, y.ctypes.data) != 0:
+        raise RuntimeError(last_error())
+    return y
+
+
 def get_factor(handle, k, dtype):
-    """(W, U) of a live dense handle (include/pogs_amd.h: PogsAmdGetFactor): k x k, k = min(m, n)."""
+    """(W, U) of a live handle with the direct projector (include/pogs_amd.h: PogsAmdGetFactor): k x k, k = min(m, n)."""
     import numpy as np
     W, U = np.zeros((k, k), dtype), np.zeros((k, k), dtype)
     if lib.PogsAmdGetFactor(handle, W.ctypes.data, U.ctypes.data) != 0:

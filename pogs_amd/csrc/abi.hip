@@ -9,12 +9,15 @@
 #include "factor_check.h"
 #include "many_kernels.h"
 #include "sparse_batch_kernels.h"
+#include "sparse_direct.h"
 #include "spmv_check.h"
 #include "prox.h"
 #include "stream.h"
 #include "vec_kernels.h"
 
 namespace pogs_amd {
+
+static_assert(kTriLower == kLower && kTriUpper == kUpper, "sparse_direct.h restates stream.h's Tri");
 
 // One factory per streaming shape and arithmetic type (dense_plan.hip, built once per entry of
 // POGS_STREAM_PLANS plus the windowed form): the shape follows from the stored row length alone,
@@ -763,6 +766,22 @@ int PogsAmdSparseCgCheck(PogsAmdSolver *s, const void *x0, const void *y0, const
     DeviceGuard guard(s->impl->device());
     s->impl->sparse_cg_check(SparseCgCheckArgs{x0, y0, x_warm, y_warm, x_prev, x12, y12, tol, max_steps, ahead, ysync, loop,
                                                x, y_new, xtemp, ytemp, r, p, sv, slots, rec_x, info, enqueued});
+    return 0;
+  });
+}
+
+int PogsAmdSparseGramCheck(int dtype, enum ORD ord, int nrows, int ncols, const int *ptr, const int *ind,
+                           const void *val, int num_cu, int window, void *G, size_t ldg, int *info) {
+  return guarded([&]() {
+    sparse_gram_check(SparseGramCheckArgs{dtype, static_cast<int>(ord), nrows, ncols, ptr, ind, val, num_cu, window, G,
+                                          ldg, info});
+    return 0;
+  });
+}
+
+int PogsAmdTriMatvecCheck(int dtype, int tri, int n, const void *M, size_t ldm, const void *x, void *y) {
+  return guarded([&]() {
+    tri_matvec_check(dtype, tri, n, M, ldm, x, y);
     return 0;
   });
 }

@@ -1,4 +1,6 @@
-// Sparse graph-form ADMM solver with the CGLS projector.
+// Sparse graph-form ADMM solver with the CGLS projector and, for a short side (min(m, n) <= POGS_AMD_SPARSE_DIRECT_MAX,
+// one GPU), the direct one: I + A^T A (or I + A A^T) formed from the sparse copies, factored and inverted once on the
+// matrix cores, applied as two triangular mat-vecs per iteration (sparse_direct.h).
 //
 // Reference call stack being replaced:
 //   PogsSparseD/S -> PogsSparse<T,O> (src/interface_c/pogs_c.cpp:57-108)
@@ -15,10 +17,12 @@
 // staged in LDS, rows reduced from there.  The solver itself runs on a tiled sliced-ELL copy of
 // each (sell.h): x slices and row sums in LDS, uint16 local columns, no partial-sum traffic.
 //
-// One translation unit in three files: sparse_kernels.h (row functors, the plain SpMV and its companions),
-// sparse_operator.h (SparseOperator<T>: both copies, their build and their products) and this one -- SparseSolver<T>
-// (equilibration, norm estimate, CGLS, the ADMM iteration, warm start, epilogue, stats) and PogsAmdSpmvCheck's
-// spmv_check(), which runs one product on a SparseOperator of its own, without a solver.
+// One translation unit in four files: sparse_kernels.h (row functors, the plain SpMV and its companions),
+// sparse_operator.h (SparseOperator<T>: both copies, their build and their products), sparse_direct.h (the direct
+// projector's kernels: sparse Gram product, triangular mat-vec) and this one -- SparseSolver<T> (equilibration, norm
+// estimate, CGLS, the direct projector's factor and solves, the ADMM iteration, warm start, epilogue, stats),
+// PogsAmdSpmvCheck's spmv_check(), which runs one product on a SparseOperator of its own, without a solver, and the
+// same for the direct projector's kernels: sparse_gram_check() and tri_matvec_check().
 #include <algorithm>
 #include <array>
 #include <cmath>
@@ -32,9 +36,11 @@
 #include "cg_fused.h"
 #include "cg_kernels.h"
 #include "engine.h"
+#include "gemm.h"
 #include "reduce.h"
 #include "sell.h"
 #include "sparse_batch_kernels.h"
+#include "sparse_direct.h"
 #include "sparse_operator.h"
 #include "spmv_check.h"
 #include "vec_kernels.h"
@@ -46,12 +52,23 @@ void rand_uniform_host(double *x, size_t n);
 
 namespace {
 
+#define POGS_STR2(x) #x
+#define POGS_STR(x) POGS_STR2(x)
+
 template <typename T>
 class SparseSolver final : public SolverBase {
  public:
   SparseSolver(int ord, size_t m, size_t n, size_t nnz, const void *data, const int *ptr, const int *ind, int mem,
                const PogsAmdOptions *opt, const PogsAmdDist *dist) {
     const double t0 = wall_s();
+    // the direct projector (ProjectorDirect, projector_direct_dense.cpp, on a sparse A): refused before anything is built
+    direct_ = opt && opt->projector == POGS_AMD_PROJ_DIRECT;
+    if (direct_) {
+      POGS_CHECK(!(dist && dist->world >= 1), "the sparse direct projector is single-GPU (the handle would have row shards)");
+      POGS_CHECK(std::min(m, n) <= static_cast<size_t>(POGS_AMD_SPARSE_DIRECT_MAX),
+                 "the sparse direct projector needs min(m, n) <= POGS_AMD_SPARSE_DIRECT_MAX = "
+                 POGS_STR(POGS_AMD_SPARSE_DIRECT_MAX) "; use POGS_AMD_PROJ_CGLS");
+    }
     ctx_.init(opt ? opt->device : -1, opt ? opt->profile : 0);
     POGS_CHECK(m > 0 && n > 0 && m < (1u << 31) && n < (1u << 31) && nnz < (1ull << 31), "bad dimensions");
     m_ = static_cast<int>(m);
@@ -73,6 +90,7 @@ class SparseSolver final : public SolverBase {
     op_->print_stamps();
     equilibrate();
     norm_est();
+    if (direct_) factor_direct();
     ctx_.sync();
     ctx_.stats.t_init_s = wall_s() - t0;
   }
@@ -110,8 +128,8 @@ class SparseSolver final : public SolverBase {
     if (p.verbose > 0 && ctx_.dist.rank() == 0) {
       print_summary(status, st.t_total_s, st.t_init_s, ctl_);
       if (p.verbose > 3) print_timing_breakdown(st.t_loop_s, st.iterations);
-      std::printf("POGS-AMD sparse/cgls: status %d, iter %u, init %.3e s, loop %.3e s, cg %llu, spmv %llu\n", status,
-                  ctl_.k, st.t_init_s, st.t_loop_s, st.cg_iters, st.matvecs);
+      std::printf("POGS-AMD sparse/%s: status %d, iter %u, init %.3e s, loop %.3e s, cg %llu, spmv %llu\n",
+                  direct_ ? "direct" : "cgls", status, ctl_.k, st.t_init_s, st.t_loop_s, st.cg_iters, st.matvecs);
     }
     return status;
   }
@@ -164,13 +182,33 @@ class SparseSolver final : public SolverBase {
     if (nrmA) *nrmA = nrmA_;
   }
 
+  // W = L^-1 and U = W^T of a direct handle: K x K row-major on the host, K = min(m, n)
+  void get_factor(void *W, void *U) override {
+    if (!direct_) SolverBase::get_factor(W, U);
+    ctx_.sync();
+    const size_t row = static_cast<size_t>(k_) * sizeof(T), pitch = kld_ * sizeof(T);
+    if (W) POGS_HIP_CHECK(hipMemcpy2D(W, row, Wp_, pitch, row, k_, hipMemcpyDeviceToHost));
+    if (U) POGS_HIP_CHECK(hipMemcpy2D(U, row, Up_, pitch, row, k_, hipMemcpyDeviceToHost));
+  }
+
   void project(const void *x0, const void *y0, double tol, void *x, void *y) override {
     hipStream_t s = ctx_.stream;
     POGS_HIP_CHECK(hipMemcpyAsync(xtemp_.p, x0, n_ * sizeof(T), hipMemcpyHostToDevice, s));
     POGS_HIP_CHECK(hipMemcpyAsync(ytemp_.p, y0, m_ * sizeof(T), hipMemcpyHostToDevice, s));
+    if (direct_) {
+      // exact: tol is not used
+      direct_project_x(xtemp_.p, ytemp_.p, x_[1].p, false);
+      if (tall_) {
+        spmv<false>(op_->A(), x_[1].p, nullptr, SpAxpbyOp<T>{1, 0, nullptr, y_[1].p}, nullptr);
+      } else {
+        launch_axpby<T>(m_, static_cast<T>(1), ytemp_.p, static_cast<T>(0), y_[1].p, s);   // y = y0 + t
+        launch_axpby<T>(m_, static_cast<T>(1), dr_.p, static_cast<T>(1), y_[1].p, s);
+      }
+    } else {
     x_[1].zero(s);  // cold start: x = 0
     cgls_project(xtemp_.p, ytemp_.p, x_[1].p, static_cast<T>(tol));
     spmv<false>(op_->A(), x_[1].p, nullptr, SpAxpbyOp<T>{1, 0, nullptr, y_[1].p}, nullptr);
+    }
     POGS_HIP_CHECK(hipMemcpyAsync(x, x_[1].p, n_ * sizeof(T), hipMemcpyDeviceToHost, s));
     POGS_HIP_CHECK(hipMemcpyAsync(y, y_[1].p, m_ * sizeof(T), hipMemcpyDeviceToHost, s));
     ctx_.sync();
@@ -180,6 +218,7 @@ class SparseSolver final : public SolverBase {
   // with the launches iteration() puts around it, minus the prox step
   void sparse_cg_check(const SparseCgCheckArgs &a) override {
     POGS_CHECK(!multi_, "PogsAmdSparseCgCheck: a row-sharded handle is not supported");
+    POGS_CHECK(!direct_, "PogsAmdSparseCgCheck: the handle runs the direct projector (no CGLS loop to check)");
     if (a.loop == 0) {
       POGS_CHECK(op_->A().sell_ready && op_->At().sell_ready,
                  "PogsAmdSparseCgCheck: the device-resident loop needs both copies tiled");
@@ -290,7 +329,7 @@ class SparseSolver final : public SolverBase {
     // device-resident CGLS loop (cg_fused.h): both copies in the tiled layout; POGS_AMD_CG=h keeps
     // round 2's host-polled loop (cgls_project), which is also what the plain-CSR fallback runs
     const char *cg_env = std::getenv("POGS_AMD_CG");
-    fused_cg_ = A.sell_ready && At.sell_ready && !(cg_env && cg_env[0] == 'h') && ctx_.poll_fetch;
+    fused_cg_ = !direct_ && A.sell_ready && At.sell_ready && !(cg_env && cg_env[0] == 'h') && ctx_.poll_fetch;
     if (multi_) {
       // every rank must take the same path (the collectives of the two loops differ): all or none
       DevBuf<double> flag(1);
@@ -447,6 +486,71 @@ class SparseSolver final : public SolverBase {
     ctx_.stats.norm_est_iters = i;
     xtemp_.zero(s);
     ctx_.stats.normest_ms = pt.stop_ms();
+  }
+
+  // ---- direct projector -------------------------------------------------------
+  // ProjectorDirect::Init and the first-call factorisation (projector_direct_dense.cpp:45-84, 116-121; s = 1 always):
+  // G = A^T A (m > n) or A A^T from the equilibrated copies (sparse_direct.h), L L^T = G + I, W = L^-1, U = W^T
+  // (gemm.h).  W and U stay; G / L and the scratch slab go back to the pool.
+  void factor_direct() {
+    hipStream_t s = ctx_.stream;
+    tall_ = m_ > n_;
+    k_ = std::min(m_, n_);
+    kld_ = round_up(static_cast<size_t>(k_), Vec16<T>::N);
+    const size_t slab = static_cast<size_t>(k_) * kld_;
+    fac_.alloc(slab * 2);
+    fac_.zero(s);
+    Wp_ = fac_.p;
+    Up_ = fac_.p + slab;
+    dr_.alloc(kld_); dt_.alloc(kld_);
+    dr_.zero(s); dt_.zero(s);
+    std::optional<DevicePool::QuiescedScope> drained;   // from the sync on: the work slabs go back as idle
+    DevBuf<T> work(slab * 2);
+    work.zero(s);
+    T *G = work.p, *tmp = work.p + slab;
+    {
+      PhaseTimer pt(s);
+      const DevCsr<T> &O = tall_ ? op_->At() : op_->A(), &I = tall_ ? op_->A() : op_->At();
+      launch_sparse_gram<T>(SparseGramArgs<T>{O.val.p, O.ind.p, O.ptr.p, I.val.p, I.ind.p, I.ptr.p, k_, 0, G, kld_},
+                            ctx_.num_cu, s);
+      POGS_HIP_CHECK(hipGetLastError());
+      ctx_.stats.gram_ms = pt.stop_ms();
+    }
+    launch_add_diag<T>(G, kld_, k_, static_cast<T>(1), s);                // projector_direct_dense.cpp:118-119
+    {
+      PhaseTimer pt(s);
+      cholesky_lower<T>(G, kld_, k_, Wp_, kld_, s);
+      ctx_.stats.chol_ms = pt.stop_ms();
+    }
+    {
+      PhaseTimer pt(s);
+      trtri_lower<T>(G, kld_, k_, Wp_, kld_, tmp, s);
+      launch_transpose<T>(Wp_, kld_, k_, k_, Up_, kld_, s);
+      ctx_.stats.trtri_ms = pt.stop_ms();
+    }
+    POGS_HIP_CHECK(hipGetLastError());
+    ctx_.sync();
+    drained.emplace();
+  }
+
+  // out = U (W rhs): the two triangular products that replace linalg_cholesky_svx (gsl_linalg.h:57-61); out may be rhs
+  void direct_solve(const T *rhs, T *out) {
+    launch_tri_matvec<T>(kTriLower, Wp_, kld_, k_, rhs, dt_.p, ctx_.stream);
+    launch_tri_matvec<T>(kTriUpper, Up_, kld_, k_, dt_.p, out, ctx_.stream);
+  }
+
+  // ProjectorDirect::Project up to the y half (projector_direct_dense.cpp:122-135): the projected x from (x0, y0).
+  //   m > n:   x = (I + A^T A)^-1 (x0 + A^T y0); the caller forms y = A x
+  //   m <= n:  t = (I + A A^T)^-1 (A x0 - y0), x = x0 - A^T t; t is left in dr_ and the caller forms y = y0 + t
+  void direct_project_x(const T *x0, const T *y0, T *x, bool timed) {
+    if (tall_) {
+      spmv_t<false>(y0, SpAxpbyOp<T>{1, 1, x0, dr_.p}, nullptr, timed);
+      direct_solve(dr_.p, x);
+    } else {
+      spmv<false>(op_->A(), x0, nullptr, SpAxpbyOp<T>{1, static_cast<T>(-1), y0, dr_.p}, nullptr, timed);
+      direct_solve(dr_.p, dr_.p);
+      spmv_t<false>(dr_.p, SpAxpbyOp<T>{static_cast<T>(-1), 1, x0, x}, nullptr, timed);
+    }
   }
 
   // ---- per solve -----------------------------------------------------------
@@ -780,11 +884,20 @@ class SparseSolver final : public SolverBase {
         reduce_y_scalars(ctx_.S.p + kGapY, 3);
       }
     }
+    if (direct_) direct_project_x(xtemp_.p, ytemp_.p, x_[nw].p, true);
     // warm start with the previous x (pogs.cpp:281), then CGLS
-    cgls_project(xtemp_.p, ytemp_.p, x_[nw].p, ctl_.proj_tol(), y_[cur_].p, x_[cur_].p);   // y_cur == A x_cur
+    else cgls_project(xtemp_.p, ytemp_.p, x_[nw].p, ctl_.proj_tol(), y_[cur_].p, x_[cur_].p);   // y_cur == A x_cur
+    if (direct_ && !tall_) {
+      // y = y0 + t as the reference forms it (projector_direct_dense.cpp:134), with the y-half bookkeeping
+      double *yp = ctx_.spart.p + static_cast<size_t>(vec_blocks(n_)) * 2;   // (the x half's partials come first)
+      hipLaunchKernelGGL(direct_wide_y_kernel<T>, dim3(vec_blocks(m_)), dim3(256), 0, s, m_, dr_.p, y_[cur_].p, y12_.p,
+                         ytemp_.p, y_[nw].p, yp);
+      ctx_.queue_sum(SumJob{yp, vec_blocks(m_), 2, ctx_.S.p + kDYprev2});
+    } else {
     // y = A x fused with the y-half bookkeeping; x-half element-wise        (projector_cgls.cpp:78)
     spmv<false>(op_->A(), x_[nw].p, nullptr, SpTailOp<T>{y_[nw].p, y_[cur_].p, y12_.p, ytemp_.p}, ctx_.S.p + kDYprev2, true);
     reduce_y_scalars(ctx_.S.p + kDYprev2, 2);
+    }
     launch_admm_tail<T>(n_, x_[nw].p, x_[cur_].p, x12_.p, xtemp_.p, ctx_.spart.p, s);
     ctx_.queue_sum(SumJob{ctx_.spart.p, vec_blocks(n_), 2, ctx_.S.p + kDXprev2});   // x side: no exchange; summed by the fetch below
     S = ctx_.fetch_scalars();
@@ -888,6 +1001,13 @@ class SparseSolver final : public SolverBase {
   DevBuf<T> cg_p_, cg_s_, cg_q_, cg_r_, cg_b_, u_;
   DevBuf<T> xout_, yout_, lout_, muout_;
   DevBuf<double> cg_;
+  // direct projector (POGS_AMD_PROJ_DIRECT; factor_direct)
+  bool direct_ = false, tall_ = true;
+  int k_ = 0;                    // min(m, n)
+  size_t kld_ = 0;               // leading dimension of W and U
+  DevBuf<T> fac_;                // [W = L^-1 | U = W^T], k_ x kld_ each
+  T *Wp_ = nullptr, *Up_ = nullptr;
+  DevBuf<T> dr_, dt_;            // right-hand side (wide: then t) and W rhs
   // device-resident CGLS loop (cg_fused.h)
   bool fused_cg_ = false;
   int cg_pred_ = 1;              // CG steps enqueued ahead: what the previous projection took
@@ -966,6 +1086,82 @@ void spmv_check_t(const SpmvCheckArgs &a) {
   for (int c = 0; c < 2; ++c) op.describe(c, a.info + 8 * c);
 }
 }  // namespace
+
+namespace {
+// PogsAmdSparseGramCheck: the copies as a handle builds them, values as given, then the launch factor_direct() runs
+template <typename T>
+void sparse_gram_check_t(const SparseGramCheckArgs &a) {
+  std::optional<DevicePool::QuiescedScope> drained;
+  Ctx ctx;
+  ctx.init(-1, 0);
+  if (a.num_cu > 0) ctx.num_cu = a.num_cu;
+  hipStream_t s = ctx.stream;
+  const int m = a.nrows, n = a.ncols, K = std::min(m, n);
+  const bool tall = m > n;
+  const size_t nnz = static_cast<size_t>(a.ptr[(a.ord == ROW_MAJ) ? m : n]);
+  SparseOperator<T> op(ctx, a.ord, m, n, nnz, a.val, a.ptr, a.ind, POGS_AMD_HOST);
+  const size_t ld = round_up(static_cast<size_t>(K), Vec16<T>::N), row = static_cast<size_t>(K) * sizeof(T);
+  DevBuf<T> G(static_cast<size_t>(K) * ld);
+  G.zero(s);
+  POGS_HIP_CHECK(hipMemcpy2DAsync(G.p, ld * sizeof(T), a.G, a.ldg * sizeof(T), row, K, hipMemcpyHostToDevice, s));
+  const DevCsr<T> &O = tall ? op.At() : op.A(), &I = tall ? op.A() : op.At();
+  const SparseGramInfo gi = launch_sparse_gram<T>(
+      SparseGramArgs<T>{O.val.p, O.ind.p, O.ptr.p, I.val.p, I.ind.p, I.ptr.p, K, a.window, G.p, ld}, ctx.num_cu, s);
+  POGS_HIP_CHECK(hipGetLastError());
+  POGS_HIP_CHECK(hipMemcpy2DAsync(a.G, a.ldg * sizeof(T), G.p, ld * sizeof(T), row, K, hipMemcpyDeviceToHost, s));
+  ctx.sync();
+  drained.emplace();
+  const int out[8] = {K, tall ? 1 : 0, gi.window, gi.windows, gi.grid, static_cast<int>(ld), 0, 0};
+  for (int i = 0; i < 8; ++i) a.info[i] = out[i];
+}
+
+template <typename T>
+void tri_matvec_check_t(int tri, int n, const T *M, size_t ldm, const T *x, T *y) {
+  POGS_CHECK(ldm % Vec16<T>::N == 0, "ldm must be a multiple of the 16-byte vector");
+  hipStream_t s = nullptr;
+  const size_t nm = static_cast<size_t>(n) * ldm;
+  DevBuf<T> dM(nm), dx(static_cast<size_t>(n)), dy(static_cast<size_t>(n));
+  POGS_HIP_CHECK(hipMemcpy(dM.p, M, nm * sizeof(T), hipMemcpyHostToDevice));
+  POGS_HIP_CHECK(hipMemcpy(dx.p, x, static_cast<size_t>(n) * sizeof(T), hipMemcpyHostToDevice));
+  POGS_HIP_CHECK(hipMemcpy(dy.p, y, static_cast<size_t>(n) * sizeof(T), hipMemcpyHostToDevice));
+  launch_tri_matvec<T>(tri, dM.p, ldm, n, dx.p, dy.p, s);
+  POGS_HIP_CHECK(hipGetLastError());
+  POGS_HIP_CHECK(hipMemcpy(y, dy.p, static_cast<size_t>(n) * sizeof(T), hipMemcpyDeviceToHost));
+  POGS_HIP_CHECK(hipDeviceSynchronize());
+}
+}  // namespace
+
+void sparse_gram_check(const SparseGramCheckArgs &a) {
+  // every refusal comes before the first HIP call
+  POGS_CHECK(a.dtype == POGS_AMD_F32 || a.dtype == POGS_AMD_F64, "unknown dtype");
+  POGS_CHECK(a.ord == ROW_MAJ || a.ord == COL_MAJ, "unknown ord (ROW_MAJ: CSR, COL_MAJ: CSC)");
+  POGS_CHECK(a.ptr && a.ind && a.val && a.G && a.info, "null argument");
+  POGS_CHECK(a.nrows >= 1 && a.ncols >= 1, "nrows and ncols must be >= 1");
+  POGS_CHECK(std::min(a.nrows, a.ncols) <= POGS_AMD_SPARSE_DIRECT_MAX,
+             "min(nrows, ncols) must be <= POGS_AMD_SPARSE_DIRECT_MAX");
+  POGS_CHECK(a.num_cu >= 0, "num_cu must be >= 0");
+  POGS_CHECK(a.window == 0 || (a.window % 64 == 0 && a.window >= 64 && a.window <= kSgWindowMax),
+             "window must be 0 (the solver's choice) or a multiple of 64 in [64, 2048]");
+  POGS_CHECK(a.ldg >= static_cast<size_t>(std::min(a.nrows, a.ncols)), "ldg must be >= min(nrows, ncols)");
+  const int r1 = (a.ord == ROW_MAJ) ? a.nrows : a.ncols;
+  POGS_CHECK(a.ptr[0] == 0, "ptr[0] must be 0");
+  POGS_CHECK(a.ptr[r1] >= 1, "ptr must end at the number of non-zeros (>= 1: an empty matrix has no product to check)");
+  if (a.dtype == POGS_AMD_F32) sparse_gram_check_t<float>(a);
+  else sparse_gram_check_t<double>(a);
+}
+
+void tri_matvec_check(int dtype, int tri, int n, const void *M, size_t ldm, const void *x, void *y) {
+  POGS_CHECK(dtype == POGS_AMD_F32 || dtype == POGS_AMD_F64, "unknown dtype");
+  POGS_CHECK(tri == kTriLower || tri == kTriUpper, "unknown tri (1 lower, 2 upper)");
+  POGS_CHECK(n >= 1, "n must be >= 1");
+  POGS_CHECK(M && x && y, "null argument");
+  POGS_CHECK(ldm >= static_cast<size_t>(n), "ldm must be >= n");
+  if (dtype == POGS_AMD_F32)
+    tri_matvec_check_t<float>(tri, n, static_cast<const float *>(M), ldm, static_cast<const float *>(x), static_cast<float *>(y));
+  else
+    tri_matvec_check_t<double>(tri, n, static_cast<const double *>(M), ldm, static_cast<const double *>(x),
+                               static_cast<double *>(y));
+}
 
 void spmv_check(const SpmvCheckArgs &a) {
   // every refusal comes before the first HIP call

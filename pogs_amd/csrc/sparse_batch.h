@@ -7,7 +7,8 @@
 // interleaved, [col][Kp], so the K values of a column are one gather.  The projection is a batched CGLS: every
 // member runs its own CG (shift 1, at most 500 steps, its own AdmmControl::proj_tol(), warm-started from its previous
 // x), a member whose CG has stopped leaves the slot list for the rest of that projection, and the host polls once
-// per CG step.
+// per CG step.  On a handle with the direct projector the projection is exact instead: two shared products and the two
+// triangular row passes of the dense batch (launch_batch_rows over W = L^-1 and U = W^T), no inner loop and no poll.
 //
 // The loop and the element-wise stages are BatchAdmm's (batch_admm.h), shared with the dense batch; here are the
 // handle check, the product, the projection and the two products of the exact residuals.
@@ -129,10 +130,43 @@ void SparseSolver<T>::solve_batch_sparse(int kb, const FnHost *f, const FnHost *
     product(MA, n, B.x12.p, ldx, B.zy.p, ldy, nullptr, static_cast<T>(0), nullptr, sl);   // A x12
     product(MT, m, B.u.p, ldy, B.zx.p, ldx, nullptr, static_cast<T>(0), nullptr, sl);     // A^T u
   };
-  B.run(project, residual_products);
+  // ProjectorDirect::Project for the problems of sl (projector_direct_dense.cpp:122-135).  The operands of the row
+  // passes keep zeros in their padding columns (launch_batch_rows multiplies them by zeros of the matrix): the products
+  // and the passes write rows below their count only.
+  const size_t ldk = tall_ ? ldx : ldy;
+  DevBuf<T> brhs, btv;
+  if (direct_) {
+    brhs.alloc(ldk * kb); btv.alloc(ldk * kb);
+    brhs.zero(s); btv.zero(s);
+  }
+  auto rows_pass = [&](int tri, const T *M, const T *X, T *Y, const BatchSlots &sl) {
+    launch_batch_rows<T>(tri, M, kld_, k_, k_, static_cast<int>(kld_), X, ldk, Y, ldk, sl, s);
+    POGS_HIP_CHECK(hipGetLastError());
+  };
+  auto project_direct = [&](const BatchSlots &sl, int nw) {
+    if (tall_) {
+      // rhs = xtemp + A^T ytemp ; x = U (W rhs) ; y = A x
+      product(MT, m, B.ytemp.p, ldy, brhs.p, ldx, B.xtemp.p, static_cast<T>(1), nullptr, sl);
+      rows_pass(kTriLower, Wp_, brhs.p, btv.p, sl);
+      rows_pass(kTriUpper, Up_, btv.p, B.x[nw].p, sl);
+      product(MA, n, B.x[nw].p, ldx, B.y[nw].p, ldy, nullptr, static_cast<T>(0), nullptr, sl);
+    } else {
+      // s = A xtemp - ytemp ; t = U (W s) ; x = xtemp - A^T t ; y = ytemp + t
+      product(MA, n, B.xtemp.p, ldx, brhs.p, ldy, B.ytemp.p, static_cast<T>(-1), nullptr, sl);
+      rows_pass(kTriLower, Wp_, brhs.p, btv.p, sl);
+      rows_pass(kTriUpper, Up_, btv.p, brhs.p, sl);
+      T *const z = B.zx.p;   // free here: A^T u of the exact residuals at another time
+      product(MT, m, brhs.p, ldy, z, ldx, nullptr, static_cast<T>(0), nullptr, sl);
+      hipLaunchKernelGGL(direct_wide_batch_kernel<T>, dim3(vbx + vby, sl.nact), dim3(256), 0, s, n, m, vbx, ldx, ldy,
+                         B.xtemp.p, z, B.x[nw].p, B.ytemp.p, brhs.p, B.y[nw].p, sl);
+      POGS_HIP_CHECK(hipGetLastError());
+    }
+  };
+  if (direct_) B.run(project_direct, residual_products);
+  else B.run(project, residual_products);
   PogsAmdStats &st = ctx_.stats;
   st.matvecs = products;
   st.cg_iters = cg_steps;
   if (B.timer.enabled()) st.reserved[7] = prod_bytes;
-  B.say_done((", " + std::to_string(cg_steps) + " CG steps").c_str());
+  B.say_done(direct_ ? ", direct projector" : (", " + std::to_string(cg_steps) + " CG steps").c_str());
 }

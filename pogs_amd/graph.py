@@ -507,6 +507,9 @@ class Solver:
     with ``shape=(m, n)`` and ``device_ptr=True`` (e.g. ``tensor.data_ptr()``).
     ``dist``: None, or ``(rank, world, m_global, unique_id_bytes)`` for a
     row-sharded solve where this process holds ``m`` consecutive rows.
+    ``projector``: PROJ_DEFAULT (dense: direct, sparse: CGLS), PROJ_CGLS, or PROJ_DIRECT -- on a sparse matrix with
+    min(m, n) <= SPARSE_DIRECT_MAX on one GPU the exact projector: two products and two triangular mat-vecs per
+    iteration instead of a CGLS loop (the one-shot ``solve_*`` calls keep CGLS).
     """
 
     def __init__(self, A, dtype=None, shape=None, device_ptr=False, order=Ordering.ROW_MAJ, device=-1,
@@ -697,8 +700,9 @@ class Solver:
         return A_eq, d, e, nrm.value
 
     def factor(self):
-        """(W, U): W = L^-1 and U = W^T of the direct projector, L L^T = I + A_eq^T A_eq (m > n) or I + A_eq A_eq^T
-        (dense solvers; include/pogs_amd.h: PogsAmdGetFactor)."""
+        """(W, U): W = L^-1 and U = W^T of the direct projector, L L^T = I + A_eq^T A_eq (m > n) or I + A_eq A_eq^T,
+        each k x k with k = min(m, n): dense solvers, and sparse ones created with projector=PROJ_DIRECT
+        (include/pogs_amd.h: PogsAmdGetFactor).  A handle that runs CGLS raises RuntimeError."""
         return _lib.get_factor(self._h, min(self._m_global or self.m, self.n), self.dtype)
 
     def project(self, x0, y0, tol=1e-8):
