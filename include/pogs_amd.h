@@ -233,7 +233,8 @@ int PogsAmdBeginRunFn(PogsAmdSolver *s, const PogsAmdFn *f, const PogsAmdFn *g,
  * Outputs are HOST arrays, problem j at offset j*n (x, mu) / j*m (y, l) / j (optval, final_iter, status);
  * y, l, mu, optval may be NULL.  Returns 0 when the batch ran (status[j] holds each PogsStatus),
  * POGS_ERROR when refused (PogsAmdLastError says why): k out of range, a sparse handle, m <= n, the CGLS projector,
- * row shards, or a NULL x, final_iter or status.  The handle's solo state (a pending warm start included) is kept. */
+ * row shards, or a NULL x, final_iter or status.  The handle's solo state (a pending warm start included) is kept.
+ * Members that start from a given (x0, l0): PogsAmdSolveBatchWarmFn. */
 #define POGS_AMD_BATCH_MAX 16
 int PogsAmdSolveBatchFn(PogsAmdSolver *s, int k, const PogsAmdFn *f, const PogsAmdFn *g, const double *rho,
                         double abs_tol, double rel_tol, unsigned int max_iter, unsigned int verbose,
@@ -252,11 +253,35 @@ int PogsAmdSolveBatchFn(PogsAmdSolver *s, int k, const PogsAmdFn *f, const PogsA
  * options.profile the products' HIP-event time (ms), launch count and algorithmic bytes.
  * Returns 0 when the batch ran (status[j] holds each PogsStatus), POGS_ERROR when refused (PogsAmdLastError says
  * why): k out of range, a dense handle, row shards, or a NULL x, final_iter or status; the handle stays usable.  The
- * handle's solo state (the last solo solve's stats but those above, its iterate, a pending warm start) is kept. */
+ * handle's solo state (the last solo solve's stats but those above, its iterate, a pending warm start) is kept.
+ * Here too every problem starts cold; members that start from a given (x0, l0): PogsAmdSolveBatchWarmFn. */
 int PogsAmdSolveBatchSparseFn(PogsAmdSolver *s, int k, const PogsAmdFn *f, const PogsAmdFn *g, const double *rho,
                               double abs_tol, double rel_tol, unsigned int max_iter, unsigned int verbose,
                               int adaptive_rho, int gap_stop, void *x, void *y, void *l, void *mu,
                               double *optval, unsigned int *final_iter, int *status);
+
+/* Batched solves whose members may start warm, on either kind of handle: a dense handle runs the batch of
+ * PogsAmdSolveBatchFn, a sparse one that of PogsAmdSolveBatchSparseFn (CGLS or direct projector).  Arguments, output
+ * layout, stats and refusals are those of the two entries (a wide or CGLS dense handle, row shards, k out of range,
+ * a NULL x, final_iter or status), and in addition:
+ * x0 (k*n), l0 (k*m): HOST arrays of the handle's dtype, problem j at offset j*n / j*m.  Both NULL: every problem
+ *    starts cold.  Both given: see `warm`.  One without the other is refused (src/cpu/pogs.cpp:159-179).
+ * warm: NULL (every problem is warm when x0 is given), or k flags: problem j starts warm where warm[j] != 0 and cold
+ *    elsewhere -- a cold problem's part of x0 / l0 is never read.  Flags together with a NULL x0 are refused.
+ * A warm problem starts as a solo solve does after PogsAmdSetWarmStart (SetInitX + SetInitLambda,
+ *    src/cpu/pogs.cpp:144-156) at its own rho[j]: x = x0 / e, y = A x, t = l0 / d, xt = (A^T t) (1 / rho[j]),
+ *    yt = t (-1 / rho[j]).  The two products are shared by the warm problems and are counted in `matvecs`.  A cold
+ *    problem returns the bytes the cold entries return for it, and a problem's outputs depend neither on k, nor on
+ *    its position, nor on the other problems, nor on which of them are warm.  The sparse CGLS batch starts its first
+ *    CG from that x.
+ * rho_final: NULL, or k doubles: each problem's rho when it stopped -- with x and l, the start of a neighbouring
+ *    problem (a warm start at rho = 1 loses most of what the warm start gains).
+ * A refused call returns POGS_ERROR, writes nothing and leaves the handle usable; the solo state is kept. */
+int PogsAmdSolveBatchWarmFn(PogsAmdSolver *s, int k, const PogsAmdFn *f, const PogsAmdFn *g, const double *rho,
+                            const void *x0, const void *l0, const int *warm,
+                            double abs_tol, double rel_tol, unsigned int max_iter, unsigned int verbose,
+                            int adaptive_rho, int gap_stop, void *x, void *y, void *l, void *mu,
+                            double *optval, unsigned int *final_iter, int *status, double *rho_final);
 
 /* Many small problems, each with its own matrix: k independent graph-form problems, problem j with its own
  * m x n matrix A_j and its own f[j], g[j], rho[j].  Each one is solved exactly as the one-shot PogsD / PogsS call

@@ -126,6 +126,9 @@ lib.PogsAmdSolveBatchFn.argtypes = [c_void_p, c_int, ctypes.POINTER(PogsAmdFn), 
                                     c_double, c_double, c_uint, c_uint, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_void_p, c_void_p, c_void_p]
 lib.PogsAmdSolveBatchSparseFn.argtypes = lib.PogsAmdSolveBatchFn.argtypes
+lib.PogsAmdSolveBatchWarmFn.argtypes = [c_void_p, c_int, ctypes.POINTER(PogsAmdFn), ctypes.POINTER(PogsAmdFn), c_void_p,
+                                        c_void_p, c_void_p, c_void_p, c_double, c_double, c_uint, c_uint, c_int, c_int,
+                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
 BATCH_MAX = 16   # include/pogs_amd.h: POGS_AMD_BATCH_MAX
 lib.PogsAmdSolveManyFn.argtypes = [c_int, c_int, c_int, c_size_t, c_size_t, c_void_p, c_int, ctypes.POINTER(PogsAmdOptions),
                                    ctypes.POINTER(PogsAmdFn), ctypes.POINTER(PogsAmdFn), c_void_p, c_double, c_double,
@@ -238,6 +241,7 @@ def pool_trim(device=-1):
 ABI_SYMBOLS = [
     "PogsD", "PogsS", "PogsSparseD", "PogsSparseS",
     "PogsAmdDistUniqueId", "PogsAmdCreateDense", "PogsAmdCreateSparse", "PogsAmdSolve", "PogsAmdSolveFn", "PogsAmdSolveBatchFn", "PogsAmdSolveBatchSparseFn",
+    "PogsAmdSolveBatchWarmFn",
     "PogsAmdSolveManyFn", "PogsAmdManyCreate", "PogsAmdManySolveFn", "PogsAmdManyGetInfo", "PogsAmdManyDestroy",
     "PogsAmdBeginRun", "PogsAmdBeginRunFn",
     "PogsAmdIterate", "PogsAmdSetWarmStart", "PogsAmdGetStats", "PogsAmdResetStats", "PogsAmdDestroy", "PogsAmdLastError",

@@ -384,7 +384,7 @@ int PogsAmdSolveBatchFn(PogsAmdSolver *s, int k, const PogsAmdFn *f, const PogsA
     DeviceGuard guard(s->impl->device());
     s->impl->solve_batch(k, fg.first.data(), fg.second.data(), rho,
                          make_params(1.0, abs_tol, rel_tol, max_iter, verbose, adaptive_rho, gap_stop),
-                         BatchOut{x, y, l, mu, optval, final_iter, status});
+                         BatchOut{x, y, l, mu, optval, final_iter, status}, BatchWarm{});
     return 0;
   }, s);
 }
@@ -400,7 +400,27 @@ int PogsAmdSolveBatchSparseFn(PogsAmdSolver *s, int k, const PogsAmdFn *f, const
     DeviceGuard guard(s->impl->device());
     s->impl->solve_batch_sparse(k, fg.first.data(), fg.second.data(), rho,
                                 make_params(1.0, abs_tol, rel_tol, max_iter, verbose, adaptive_rho, gap_stop),
-                                BatchOut{x, y, l, mu, optval, final_iter, status});
+                                BatchOut{x, y, l, mu, optval, final_iter, status}, BatchWarm{});
+    return 0;
+  }, s);
+}
+
+int PogsAmdSolveBatchWarmFn(PogsAmdSolver *s, int k, const PogsAmdFn *f, const PogsAmdFn *g, const double *rho,
+                            const void *x0, const void *l0, const int *warm, double abs_tol, double rel_tol,
+                            unsigned int max_iter, unsigned int verbose, int adaptive_rho, int gap_stop, void *x, void *y,
+                            void *l, void *mu, double *optval, unsigned int *final_iter, int *status, double *rho_final) {
+  return guarded([&]() {
+    POGS_CHECK(s && s->impl, "null solver");
+    POGS_CHECK(k >= 1 && k <= POGS_AMD_BATCH_MAX, "batched solve: k must be in [1, POGS_AMD_BATCH_MAX]");
+    POGS_CHECK((x0 != nullptr) == (l0 != nullptr), "batched solve: a warm start needs both x0 and l0 (pogs.cpp:159-179)");
+    POGS_CHECK(x0 || !warm, "batched solve: warm flags without x0 and l0");
+    const auto fg = fn_hosts("batched solve", k, f, g, x, final_iter, status);
+    DeviceGuard guard(s->impl->device());
+    BatchWarm w;
+    w.x0 = x0; w.l0 = l0; w.warm = warm; w.rho_final = rho_final;
+    s->impl->solve_batch_any(k, fg.first.data(), fg.second.data(), rho,
+                             make_params(1.0, abs_tol, rel_tol, max_iter, verbose, adaptive_rho, gap_stop),
+                             BatchOut{x, y, l, mu, optval, final_iter, status}, w);
     return 0;
   }, s);
 }

@@ -7,6 +7,8 @@
 // function tables, the controls, the element-wise stages (batch_kernels.hip), the one poll per iteration, and the
 // rule that keeps a member's bytes independent of its batch and slot: a problem that stops is finished from the
 // iterate of that iteration and leaves the slot list; nothing of it is touched again.
+// Members may start warm (warm_begin, between the constructor and run()): from a caller's (x0, l0) at their own rho,
+// through the same residual_products.
 #pragma once
 #include <algorithm>
 #include <array>
@@ -142,6 +144,53 @@ struct BatchAdmm {
     if (p.verbose > 0)
       std::printf("POGS-AMD %s batch: problem %d, status %d, iter %u, rho %.3e\n", label, j, out.status[j], ctl[j].k,
                   static_cast<double>(ctl[j].rho));
+  }
+
+  // The warm begin, between the constructor and run(): every member j that w lists starts from the caller's
+  // (x0, l0) at its own rho as a solo solve does after SetInitX + SetInitLambda (pogs.cpp:144-156; dense_iter.h
+  // apply_warm_start): x = x0 / e, y = A x, t = l0 / d, xt = (A^T t) (1 / rho_j), yt = t (-1 / rho_j); xtemp and
+  // ytemp stay zero.  One scaling launch, the back end's two shared products over the warm members only, one closing
+  // launch.  A cold member's vectors are not touched and its x0 / l0 are not read; the padding stays zero.
+  template <typename Products>
+  void warm_begin(const BatchWarm &w, Products &&residual_products) {
+    std::vector<int> warm;
+    for (int j = 0; j < kb; ++j)
+      if (w.is_warm(j)) warm.push_back(j);
+    if (warm.empty()) return;
+    DevBuf<T> x0(ldx * kb), l0(ldy * kb);
+    const T *hx = static_cast<const T *>(w.x0), *hl = static_cast<const T *>(w.l0);
+    // one strided copy per run of consecutive warm members (two in all when every member is warm)
+    for (size_t q = 0; q < warm.size();) {
+      size_t r = q + 1;
+      while (r < warm.size() && warm[r] == warm[r - 1] + 1) ++r;
+      const size_t j0 = static_cast<size_t>(warm[q]), cnt = r - q;
+      POGS_HIP_CHECK(hipMemcpy2DAsync(x0.p + j0 * ldx, ldx * sizeof(T), hx + j0 * n, n * sizeof(T), n * sizeof(T), cnt,
+                                      hipMemcpyHostToDevice, s));
+      POGS_HIP_CHECK(hipMemcpy2DAsync(l0.p + j0 * ldy, ldy * sizeof(T), hl + j0 * m, m * sizeof(T), m * sizeof(T), cnt,
+                                      hipMemcpyHostToDevice, s));
+      q = r;
+    }
+    BatchWarmArgs<T> a;
+    a.n = n; a.m = m; a.bx = vbx; a.by = vby; a.ldx = ldx; a.ldy = ldy;
+    a.sl = slots_of(warm);
+    a.x0 = x0.p; a.l0 = l0.p; a.d = d; a.e = e;
+    a.x12 = x12.p; a.u = u.p; a.zx = zx.p; a.zy = zy.p;
+    a.x_cur = x[cur].p; a.y_cur = y[cur].p; a.xt = xt.p; a.yt = yt.p;
+    for (int j = 0; j < kBatchMax; ++j) {
+      a.pos[j] = j < kb ? static_cast<T>(1) / ctl[j].rho : 0;
+      a.neg[j] = j < kb ? static_cast<T>(-1) / ctl[j].rho : 0;
+    }
+    launch_batch_warm_scale<T>(a, s);
+    POGS_HIP_CHECK(hipGetLastError());
+    residual_products(a.sl);   // zy = A x12, zx = A^T u
+    launch_batch_warm_close<T>(a, s);
+    POGS_HIP_CHECK(hipGetLastError());
+    POGS_HIP_CHECK(hipStreamSynchronize(s));   // x0 and l0 are freed at scope exit
+  }
+  // each member's rho at its stop (nothing of a member changes after it)
+  void rho_out(double *rho_final) const {
+    if (!rho_final) return;
+    for (int j = 0; j < kb; ++j) rho_final[j] = static_cast<double>(ctl[j].rho);
   }
 
   // Runs every problem to its stop; leaves iterations and reserved[4..6] in the handle's stats (matvecs, cg_iters and

@@ -82,6 +82,23 @@ template <typename T> void launch_batch_exact_u(const BatchVecArgs<T> &a, hipStr
 template <typename T> void launch_batch_exact(const BatchVecArgs<T> &a, hipStream_t s);
 void launch_batch_sums(const BatchSumJobs &jobs, int njobs, const BatchSlots &sl, double *out, hipStream_t s);
 
+// The warm begin of the listed problems (BatchAdmm::warm_begin; pogs.cpp:144-156), around the two products
+// zy = A x12, zx = A^T u.  x0 / l0: the caller's start, problem p at p * ldx / p * ldy.  Elements below n / m only:
+// the padding of every vector stays zero.
+template <typename T>
+struct BatchWarmArgs {
+  int n, m, bx, by;
+  size_t ldx, ldy;
+  BatchSlots sl;
+  const T *x0, *l0, *d, *e;
+  T *x12, *u;                        // scale: x12 = x0 / e, u = l0 / d
+  const T *zx, *zy;                  // close: A^T u, A x12
+  T *x_cur, *y_cur, *xt, *yt;        // close: x = x12, y = zy, xt = zx * pos, yt = u * neg
+  T pos[kBatchMax], neg[kBatchMax];  // T(1) / rho and T(-1) / rho, by problem index
+};
+template <typename T> void launch_batch_warm_scale(const BatchWarmArgs<T> &a, hipStream_t s);
+template <typename T> void launch_batch_warm_close(const BatchWarmArgs<T> &a, hipStream_t s);
+
 // The slots of the diagnostic entries (PogsAmdBatchRowsCheck, ...): k problems, nact of them active, act without
 // repeats and inside [0, k).  Throws Error otherwise.
 inline BatchSlots checked_batch_slots(int k, const int *act, int nact) {

@@ -280,6 +280,40 @@ __global__ void __launch_bounds__(kVecTpb) batch_exact_kernel(BatchVecArgs<T> a)
   if (threadIdx.x == 0) a.part[static_cast<size_t>(p) * (a.bx + a.by) + blockIdx.x] = acc[0];
 }
 
+// warm begin, before the products: x12 = x0 / e (x blocks), u = l0 / d (y blocks)   (pogs.cpp:146, 152)
+template <typename T>
+__global__ void __launch_bounds__(kVecTpb) batch_warm_scale_kernel(BatchWarmArgs<T> a) {
+  const int p = a.sl.act[blockIdx.y];
+  const bool is_x = static_cast<int>(blockIdx.x) < a.bx;
+  const int blk = is_x ? blockIdx.x : blockIdx.x - a.bx;
+  const int e = blk * kVecTpb + threadIdx.x;
+  if (is_x && e < a.n) {
+    const size_t o = static_cast<size_t>(p) * a.ldx + e;
+    a.x12[o] = a.x0[o] / a.e[e];
+  } else if (!is_x && e < a.m) {
+    const size_t o = static_cast<size_t>(p) * a.ldy + e;
+    a.u[o] = a.l0[o] / a.d[e];
+  }
+}
+
+// warm begin, after the products: x = x0 / e, xt = (A^T t) (1 / rho) (x blocks); y = A x, yt = t (-1 / rho) (y blocks)
+template <typename T>
+__global__ void __launch_bounds__(kVecTpb) batch_warm_close_kernel(BatchWarmArgs<T> a) {
+  const int p = a.sl.act[blockIdx.y];
+  const bool is_x = static_cast<int>(blockIdx.x) < a.bx;
+  const int blk = is_x ? blockIdx.x : blockIdx.x - a.bx;
+  const int e = blk * kVecTpb + threadIdx.x;
+  if (is_x && e < a.n) {
+    const size_t o = static_cast<size_t>(p) * a.ldx + e;
+    a.x_cur[o] = a.x12[o];
+    a.xt[o] = a.zx[o] * a.pos[p];
+  } else if (!is_x && e < a.m) {
+    const size_t o = static_cast<size_t>(p) * a.ldy + e;
+    a.y_cur[o] = a.zy[o];
+    a.yt[o] = a.u[o] * a.neg[p];
+  }
+}
+
 __global__ void __launch_bounds__(256) batch_sum_kernel(BatchSumJobs jobs, BatchSlots sl, double *out) {
   __shared__ double s_red[3 * 4];
   const BatchSumJob jb = jobs.j[blockIdx.x];
@@ -343,6 +377,14 @@ void launch_batch_exact(const BatchVecArgs<T> &a, hipStream_t s) {
 }
 void launch_batch_sums(const BatchSumJobs &jobs, int njobs, const BatchSlots &sl, double *out, hipStream_t s) {
   hipLaunchKernelGGL(batch_sum_kernel, dim3(njobs, sl.nact), dim3(256), 0, s, jobs, sl, out);
+}
+template <typename T>
+void launch_batch_warm_scale(const BatchWarmArgs<T> &a, hipStream_t s) {
+  hipLaunchKernelGGL(batch_warm_scale_kernel<T>, dim3(a.bx + a.by, a.sl.nact), dim3(kVecTpb), 0, s, a);
+}
+template <typename T>
+void launch_batch_warm_close(const BatchWarmArgs<T> &a, hipStream_t s) {
+  hipLaunchKernelGGL(batch_warm_close_kernel<T>, dim3(a.bx + a.by, a.sl.nact), dim3(kVecTpb), 0, s, a);
 }
 
 template <typename T>
@@ -409,6 +451,8 @@ void batch_cols_check(int rows, int cols, const T *M, size_t ldm, int k, const i
   template void launch_batch_tail<T>(const BatchVecArgs<T> &, hipStream_t);                                            \
   template void launch_batch_exact_u<T>(const BatchVecArgs<T> &, hipStream_t);                                         \
   template void launch_batch_exact<T>(const BatchVecArgs<T> &, hipStream_t);                                          \
+  template void launch_batch_warm_scale<T>(const BatchWarmArgs<T> &, hipStream_t);                                    \
+  template void launch_batch_warm_close<T>(const BatchWarmArgs<T> &, hipStream_t);                                    \
   template void batch_rows_check<T>(int, int, int, const T *, size_t, int, const int *, int, const T *, size_t, T *,  \
                                     size_t);                                                                           \
   template void batch_cols_check<T>(int, int, const T *, size_t, int, const int *, int, const T *, size_t, const T *, \

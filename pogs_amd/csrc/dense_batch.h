@@ -16,7 +16,7 @@
 
 template <typename T, typename Tag>
 void DenseSolver<T, Tag>::solve_batch(int kb, const FnHost *f, const FnHost *g, const double *rho0,
-                                      const SolveParams &p, const BatchOut &out) {
+                                      const SolveParams &p, const BatchOut &out, const BatchWarm &w) {
   POGS_CHECK(!multi_, "batched solves are single-GPU (the handle has row shards)");
   POGS_CHECK(!use_cgls_, "batched solves need the direct projector (the handle uses CGLS)");
   POGS_CHECK(tall_ && !tmode_, "batched solves need m > n (the handle stores A^T)");
@@ -60,7 +60,9 @@ void DenseSolver<T, Tag>::solve_batch(int kb, const FnHost *f, const FnHost *g, 
     cols_pass(B.u.p, nullptr, B.zx.p, sl);
     passes += 2;
   };
+  B.warm_begin(w, residual_products);
   B.run(project, residual_products);
+  B.rho_out(w.rho_final);
   PogsAmdStats &st = ctx_.stats;
   st.matvecs = passes;
   if (B.timer.enabled()) st.reserved[7] = st.reserved[6] * m * n * sizeof(T);

@@ -217,9 +217,13 @@ class DenseSolver final : public SolverBase {
 
   // Batched solves (the loop: batch_admm.h; its passes over the stored matrices: dense_batch.h): separate buffers; the
   // solo state, a pending warm start and the stats of the last solo solve stay as they are (except iterations, matvecs
-  // and reserved[4..7]).
+  // and reserved[4..7]).  w: the members that start warm, cold by default.
   void solve_batch(int k, const FnHost *f, const FnHost *g, const double *rho, const SolveParams &p,
-                   const BatchOut &out) override;
+                   const BatchOut &out, const BatchWarm &w) override;
+  void solve_batch_any(int k, const FnHost *f, const FnHost *g, const double *rho, const SolveParams &p,
+                       const BatchOut &out, const BatchWarm &w) override {
+    solve_batch(k, f, g, rho, p, out, w);
+  }
 
   void set_warm_start(const void *x0, const void *l0) override {
     warm_x_.assign(static_cast<const T *>(x0), static_cast<const T *>(x0) + n_);

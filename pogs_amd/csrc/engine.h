@@ -679,6 +679,16 @@ struct BatchOut {
   int *status;
 };
 
+// Start and extra output of a batched solve (PogsAmdSolveBatchWarmFn): HOST arrays.  x0 (k n) and l0 (k m) are both
+// null (every problem starts cold) or both given; warm: null (every problem is warm when x0 is given) or k flags;
+// rho_final: null or k doubles.  The default is the cold batch of PogsAmdSolveBatchFn / PogsAmdSolveBatchSparseFn.
+struct BatchWarm {
+  const void *x0 = nullptr, *l0 = nullptr;
+  const int *warm = nullptr;
+  double *rho_final = nullptr;
+  bool is_warm(int j) const { return x0 && (!warm || warm[j] != 0); }
+};
+
 // PogsAmdSparseCgCheck (include/pogs_amd.h, Part 3): HOST arrays of the handle's type, n- or m-sized as named there
 struct SparseCgCheckArgs {
   const void *x0, *y0, *x_warm, *y_warm, *x_prev, *x12, *y12;
@@ -700,14 +710,18 @@ struct SolverBase {
                     void *mu, double *optval, unsigned *final_iter) = 0;
   virtual void begin_run(const FnHost &f, const FnHost &g, const SolveParams &p) = 0;
   // k problems on the handle's matrix (dense, m > n, direct projector, one GPU); rho: k values or null
-  virtual void solve_batch(int, const FnHost *, const FnHost *, const double *, const SolveParams &, const BatchOut &) {
+  virtual void solve_batch(int, const FnHost *, const FnHost *, const double *, const SolveParams &, const BatchOut &,
+                           const BatchWarm &) {
     throw Error("batched solves need a dense handle");
   }
   // k problems on the handle's sparse matrix (one GPU); rho: k values or null
   virtual void solve_batch_sparse(int, const FnHost *, const FnHost *, const double *, const SolveParams &,
-                                  const BatchOut &) {
+                                  const BatchOut &, const BatchWarm &) {
     throw Error("a batched sparse solve needs a sparse handle");
   }
+  // whichever of the two the handle has (PogsAmdSolveBatchWarmFn)
+  virtual void solve_batch_any(int k, const FnHost *f, const FnHost *g, const double *rho, const SolveParams &p,
+                               const BatchOut &out, const BatchWarm &w) = 0;
   virtual void iterate(unsigned iters, double *seconds, unsigned *solves) = 0;
   virtual void set_warm_start(const void *x0, const void *l0) = 0;
   virtual void get_equil(void *A_eq, void *d, void *e, double *nrmA) = 0;

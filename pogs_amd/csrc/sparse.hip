@@ -142,9 +142,13 @@ class SparseSolver final : public SolverBase {
   }
 
   // k problems on the handle's matrix, every product with A / A^T shared (the loop: batch_admm.h; the
-  // products and the batched CGLS: sparse_batch.h)
+  // products and the batched CGLS: sparse_batch.h); w: the members that start warm, cold by default
   void solve_batch_sparse(int kb, const FnHost *f, const FnHost *g, const double *rho0, const SolveParams &p,
-                          const BatchOut &out) override;
+                          const BatchOut &out, const BatchWarm &w) override;
+  void solve_batch_any(int kb, const FnHost *f, const FnHost *g, const double *rho0, const SolveParams &p,
+                       const BatchOut &out, const BatchWarm &w) override {
+    solve_batch_sparse(kb, f, g, rho0, p, out, w);
+  }
 
   void set_warm_start(const void *x0, const void *l0) override {
     warm_x_.assign(static_cast<const T *>(x0), static_cast<const T *>(x0) + n_);

@@ -21,7 +21,7 @@
 
 template <typename T>
 void SparseSolver<T>::solve_batch_sparse(int kb, const FnHost *f, const FnHost *g, const double *rho0,
-                                         const SolveParams &p, const BatchOut &out) {
+                                         const SolveParams &p, const BatchOut &out, const BatchWarm &w) {
   POGS_CHECK(!multi_, "batched sparse solves are single-GPU (the handle has row shards)");
   hipStream_t s = ctx_.stream;
   const int n = n_, m = m_;
@@ -162,8 +162,10 @@ void SparseSolver<T>::solve_batch_sparse(int kb, const FnHost *f, const FnHost *
       POGS_HIP_CHECK(hipGetLastError());
     }
   };
+  B.warm_begin(w, residual_products);   // (the batched CGLS then starts from x[cur] with y[cur] = A x[cur])
   if (direct_) B.run(project_direct, residual_products);
   else B.run(project, residual_products);
+  B.rho_out(w.rho_final);
   PogsAmdStats &st = ctx_.stats;
   st.matvecs = products;
   st.cg_iters = cg_steps;

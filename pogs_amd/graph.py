@@ -293,28 +293,51 @@ def solve_lasso(A, b, lambd, abs_tol=1e-4, rel_tol=1e-4, max_iter=2500, verbose=
     return _solve_graph_form(A, f, g, abs_tol, rel_tol, max_iter, verbose, rho, dtype=dtype)
 
 
-def _solve_path(A, b, lambdas, make_fg, abs_tol, rel_tol, max_iter, verbose, rho, dtype):
+def _chain_schedule(P, slots=None):
+    """The rounds of `Solver.solve_chain` for P problems: with slots = min(BATCH_MAX, slots or BATCH_MAX) (so None
+    and 0 both mean BATCH_MAX; a negative value is a ValueError) and L = ceil(P / slots), segment s is the indices [s L, min((s + 1) L, P)) and round r holds element r of every
+    segment that has one.  Returns a list of rounds, each a list of (index, predecessor): the predecessor is
+    index - 1, solved one round earlier in the same segment, or None for the first element of a segment."""
+    slots = min(_lib.BATCH_MAX, int(slots) if slots else _lib.BATCH_MAX)
+    if slots < 1:
+        raise ValueError("solve_chain: slots must be >= 1")
+    if P <= 0:
+        return []
+    L = -(-P // slots)
+    return [[(s0 + r, s0 + r - 1 if r else None) for s0 in range(0, P, L) if s0 + r < min(s0 + L, P)]
+            for r in range(L)]
+
+
+def _solve_path(A, b, lambdas, make_fg, abs_tol, rel_tol, max_iter, verbose, rho, dtype, chain=False, slots=None):
     lambdas = [float(v) for v in np.atleast_1d(lambdas)]
     m, n = _shape(A)
     pairs = [make_fg(b, lam, n) for lam in lambdas]
     with Solver(A, dtype=dtype) as s:
-        res = s.solve_batch([p[0] for p in pairs], [p[1] for p in pairs], rho=rho, abs_tol=abs_tol, rel_tol=rel_tol,
-                            max_iter=max_iter, verbose=verbose)
+        if chain:
+            res = s.solve_chain([p[0] for p in pairs], [p[1] for p in pairs], rho=rho, slots=slots, abs_tol=abs_tol,
+                                rel_tol=rel_tol, max_iter=max_iter, verbose=verbose)
+        else:
+            res = s.solve_batch([p[0] for p in pairs], [p[1] for p in pairs], rho=rho, abs_tol=abs_tol,
+                                rel_tol=rel_tol, max_iter=max_iter, verbose=verbose)
     return {"x": np.stack([r["x"] for r in res]) if res else np.zeros((0, n), _resolve_dtype(dtype)),
             "optval": np.array([r["optval"] for r in res]),
             "iterations": np.array([r["iterations"] for r in res], dtype=np.int64),
             "status": np.array([r["status"] for r in res], dtype=np.int64)}
 
 
-def solve_lasso_path(A, b, lambdas, abs_tol=1e-4, rel_tol=1e-4, max_iter=2500, verbose=0, rho=1.0, dtype=None):
+def solve_lasso_path(A, b, lambdas, abs_tol=1e-4, rel_tol=1e-4, max_iter=2500, verbose=0, rho=1.0, dtype=None,
+                     chain=False, slots=None):
     """The lasso for every lambda of `lambdas` on one matrix, as batched solves (Solver.solve_batch).
+    ``chain``: solve them as warm-started batches instead (Solver.solve_chain over at most ``slots`` segments of
+    the list as given: pass the lambdas sorted), each lambda but the first of its segment started from its neighbour.
     Returns {'x': K x n, 'optval', 'iterations', 'status': length K}."""
-    return _solve_path(A, b, lambdas, lasso_functions, abs_tol, rel_tol, max_iter, verbose, rho, dtype)
+    return _solve_path(A, b, lambdas, lasso_functions, abs_tol, rel_tol, max_iter, verbose, rho, dtype, chain, slots)
 
 
-def solve_logistic_path(A, b, lambdas, abs_tol=1e-4, rel_tol=1e-4, max_iter=2500, verbose=0, rho=1.0, dtype=None):
+def solve_logistic_path(A, b, lambdas, abs_tol=1e-4, rel_tol=1e-4, max_iter=2500, verbose=0, rho=1.0, dtype=None,
+                        chain=False, slots=None):
     """L1-regularised logistic regression for every lambda of `lambdas`, as batched solves (see solve_lasso_path)."""
-    return _solve_path(A, b, lambdas, logistic_functions, abs_tol, rel_tol, max_iter, verbose, rho, dtype)
+    return _solve_path(A, b, lambdas, logistic_functions, abs_tol, rel_tol, max_iter, verbose, rho, dtype, chain, slots)
 
 
 def _fn_struct(f, count, dtype, keep):
@@ -612,12 +635,16 @@ class Solver:
                 "status": status}
 
     def solve_batch(self, fs, gs, rho=1.0, abs_tol=1e-4, rel_tol=1e-4, max_iter=2500, verbose=0, adaptive_rho=True,
-                    gap_stop=True):
+                    gap_stop=True, x0=None, l0=None, warm=None, return_rho=False):
         """Solve len(fs) problems (f_j, g_j, rho_j) on this handle's matrix, every pass over A shared by up to
         BATCH_MAX of them (include/pogs_amd.h: PogsAmdSolveBatchFn on a dense handle -- m > n, direct projector,
         one GPU; PogsAmdSolveBatchSparseFn on a sparse one -- any shape, one GPU).
         ``rho``: one value for all or a sequence.  Longer lists run as consecutive batches.  Returns a list of
-        dicts with the keys `solve` returns.  The handle's solo state (a pending warm start included) is kept."""
+        dicts with the keys `solve` returns.  The handle's solo state (a pending warm start included) is kept.
+        ``x0`` / ``l0``: sequences of len(fs) starts (length n / m), both or neither; problem j starts from
+        (x0[j], l0[j]) at rho_j as a solo solve does after `warm_start` (PogsAmdSolveBatchWarmFn).  ``warm``: len(fs)
+        flags, the problems that do so (default: all of them); an entry of x0 / l0 may be None where its flag is
+        false.  With a start or ``return_rho`` each dict also carries "rho", the problem's rho when it stopped."""
         fs, gs = list(fs), list(gs)
         k = len(fs)
         if len(gs) != k:
@@ -632,6 +659,8 @@ class Solver:
             if len(f) != self.m or len(g) != self.n:
                 raise ValueError("solve_batch: f must have length %d and g length %d, got %d and %d"
                                  % (self.m, self.n, len(f), len(g)))
+        starts = self._batch_starts(k, x0, l0, warm)
+        plain = starts is None and not return_rho
         entry = lib.PogsAmdSolveBatchSparseFn if self.sparse else lib.PogsAmdSolveBatchFn
         out = []
         for lo in range(0, k, _lib.BATCH_MAX):
@@ -652,16 +681,90 @@ class Solver:
             optval = np.zeros(kb, np.float64)
             final_iter = np.zeros(kb, np.uint32)
             status = np.zeros(kb, np.int32)
-            st = entry(self._h, kb, fa, ga, _ptr(r), abs_tol, rel_tol, int(max_iter), int(verbose), int(adaptive_rho),
-                       int(gap_stop), _ptr(x), _ptr(y), _ptr(l), _ptr(mu), _ptr(optval), _ptr(final_iter),
-                       _ptr(status))
+            if plain:
+                st = entry(self._h, kb, fa, ga, _ptr(r), abs_tol, rel_tol, int(max_iter), int(verbose),
+                           int(adaptive_rho), int(gap_stop), _ptr(x), _ptr(y), _ptr(l), _ptr(mu), _ptr(optval),
+                           _ptr(final_iter), _ptr(status))
+            else:
+                rho_final = np.zeros(kb, np.float64)
+                xs = ls = flags = None
+                if starts is not None and any(starts[2][lo:hi]):
+                    xs = np.ascontiguousarray(starts[0][lo:hi])
+                    ls = np.ascontiguousarray(starts[1][lo:hi])
+                    flags = np.ascontiguousarray(starts[2][lo:hi], dtype=np.int32)
+                st = lib.PogsAmdSolveBatchWarmFn(self._h, kb, fa, ga, _ptr(r), None if xs is None else _ptr(xs),
+                                                 None if ls is None else _ptr(ls),
+                                                 None if flags is None else _ptr(flags), abs_tol, rel_tol,
+                                                 int(max_iter), int(verbose), int(adaptive_rho), int(gap_stop), _ptr(x),
+                                                 _ptr(y), _ptr(l), _ptr(mu), _ptr(optval), _ptr(final_iter),
+                                                 _ptr(status), _ptr(rho_final))
             del keep
             if st != 0:
                 raise RuntimeError("pogs_amd: batched solve failed: " + _lib.last_error())
             for j in range(kb):
                 out.append({"x": x[j], "y": y[j], "l": l[j], "mu": mu[j], "optval": float(optval[j]),
                             "iterations": int(final_iter[j]), "status": int(status[j])})
+                if not plain:
+                    out[-1]["rho"] = float(rho_final[j])
         return out
+
+    def _batch_starts(self, k, x0, l0, warm):
+        """The starts of `solve_batch` as (k x n array, k x m array, k flags), or None when every problem is cold;
+        ValueError for a start that does not fit.  Rows of cold problems are zero (they are never read)."""
+        if x0 is None and l0 is None:
+            if warm is not None and any(bool(w) for w in warm):
+                raise ValueError("solve_batch: warm flags without x0 and l0")
+            return None
+        if x0 is None or l0 is None:
+            raise ValueError("solve_batch: a warm start needs both x0 and l0")
+        x0, l0 = list(x0), list(l0)
+        flags = [True] * k if warm is None else [bool(w) for w in warm]
+        if len(x0) != k or len(l0) != k or len(flags) != k:
+            raise ValueError("solve_batch: %d problems, %d x0, %d l0 and %d warm flags" % (k, len(x0), len(l0), len(flags)))
+        xs = np.zeros((k, self.n), self.dtype)
+        ls = np.zeros((k, self.m), self.dtype)
+        for j in range(k):
+            if not flags[j]:
+                continue
+            if x0[j] is None or l0[j] is None:
+                raise ValueError("solve_batch: problem %d is warm and has no x0 / l0" % j)
+            xj, lj = np.asarray(x0[j], self.dtype), np.asarray(l0[j], self.dtype)
+            if xj.shape != (self.n,) or lj.shape != (self.m,):
+                raise ValueError("solve_batch: x0[%d] must have length %d and l0[%d] length %d" % (j, self.n, j, self.m))
+            xs[j], ls[j] = xj, lj
+        return xs, ls, flags
+
+    def solve_chain(self, fs, gs, rho=1.0, slots=None, abs_tol=1e-4, rel_tol=1e-4, max_iter=2500, verbose=0,
+                    adaptive_rho=True, gap_stop=True):
+        """Solve problems whose neighbours in list order are similar (a sorted regularisation path) as warm-started
+        batches: the list is cut into at most ``slots`` (default and at most BATCH_MAX) consecutive segments, round r
+        solves element r of every segment in one batch (`_chain_schedule`), and each problem but the first of its
+        segment starts from its predecessor's x, l and final rho.  The first of a segment, and the successor of a
+        problem that ended neither solved nor at max_iter, starts cold at ``rho``.  Returns the list of dicts of
+        `solve_batch` (with "rho") in problem order."""
+        fs, gs = list(fs), list(gs)
+        P = len(fs)
+        if len(gs) != P:
+            raise ValueError("solve_chain: %d f and %d g function vectors" % (P, len(gs)))
+        res = [None] * P
+        for rnd in _chain_schedule(P, slots):
+            idx = [j for j, _ in rnd]
+            x0, l0, warm, rhos = [], [], [], []
+            for j, pred in rnd:
+                prev = res[pred] if pred is not None else None
+                ok = prev is not None and prev["status"] in (POGS_SUCCESS, POGS_MAX_ITER)
+                warm.append(ok)
+                x0.append(prev["x"] if ok else None)
+                l0.append(prev["l"] if ok else None)
+                rhos.append(prev["rho"] if ok else float(rho))
+            kw = dict(rho=rhos, abs_tol=abs_tol, rel_tol=rel_tol, max_iter=max_iter, verbose=verbose,
+                      adaptive_rho=adaptive_rho, gap_stop=gap_stop, return_rho=True)
+            if any(warm):
+                kw.update(x0=x0, l0=l0, warm=warm)
+            got = self.solve_batch([fs[j] for j in idx], [gs[j] for j in idx], **kw)
+            for j, r in zip(idx, got):
+                res[j] = r
+        return res
 
     def begin_run(self, f, g, abs_tol=1e-4, rel_tol=1e-4, max_iter=2500, rho=1.0, adaptive_rho=True, gap_stop=True):
         args, keep = self._coef(f, g)
