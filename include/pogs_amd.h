@@ -595,6 +595,74 @@ int PogsAmdSparseGramCheck(int dtype, enum ORD ord, int nrows, int ncols, const 
  * lower triangle (columns 0 .. i of row i), 2: the upper one (columns i .. n - 1); x, y: n elements.  Nothing outside
  * the triangle and nothing in columns n .. ldm is read. */
 int PogsAmdTriMatvecCheck(int dtype, int tri, int n, const void *M, size_t ldm, const void *x, void *y);
+/* Diagnostic of the dense streaming passes (csrc/stream.h) and of the column side between two passes
+ * (csrc/fused_cols.h): ONE pass over a stored matrix and its second stage on caller-supplied HOST arrays, by the
+ * launch functions and kernel instantiations a dense solve uses (the per-shape objects of csrc/dense_plan.hip).  No
+ * iteration is modelled: every output is a function of this call's inputs alone.
+ *   M: rows x ldm row-major, ldm a multiple of VEC and >= n_pad = round_up(n, VEC).  Contract of the caller, as the
+ *   solver's buffers keep it: M's columns n .. n_pad and the entries n .. n_pad of x0 / x1 are ZERO; nothing in columns
+ *   n_pad .. ldm is read.  W_SWEEP (rows == n, the lower triangle of M): a row is read in whole 16-byte vectors up to
+ *   and including the vector that holds its diagonal, so the entries right of the diagonal inside that vector must be
+ *   zero; no vector wholly right of the diagonal is read.
+ *   The shape is make_stream_plan(n_pad, num_cu) (num_cu = 0: the device's; POGS_AMD_XL_LIMIT is honoured), or the shape
+ *   (force_tpb, force_nv) of POGS_STREAM_PLANS when force_tpb != 0: it must hold n_pad (tpb nv VEC >= n_pad).  The
+ *   per-solve tuning of the one-pass kernel (workgroups per CU, the prefetching kernel of fp32 256 x 5 with the logistic
+ *   functor) is applied as a solve applies it.
+ *   form / functor (pass, then second stage):
+ *     PRE_ACC    the column-sum-only pass.  functor CHEAP: u0 = ytemp, u1 = y12 + zs yt - ycur (PreAccOp); XSIDE:
+ *                u0 = ytemp, u1 = y12 (PreAcc2Op).
+ *     ITER_FULL  the one-pass iteration's pass, two dots (x0, x1) and two column sums, functor FusedIterOp with the
+ *                inlined cheap prox (CHEAP), the logistic prox (LOGISTIC) or the m <= n mirror (XSIDE: yt is the old
+ *                dual vector, c_old its scale).  Row outputs ynew, ytemp (in / out), y12s, ytemps; scalars[0..6).
+ *     ITER_LEAN  the same with one dot and one column sum (fp64 only: POGS_ERROR in fp32); scalars[2] stays 0.
+ *     EXACT      the exact-residual pass: dot with x0, ExactRowOp (y12, yt, ycur, zs) -> scalars[0]; second stage
+ *                ExactColOp (x12 as INPUT, xt, x_cur, zs) -> col_scalars[0]; tot0 = the raw column totals.  This is
+ *                the form that runs on windowed plans.
+ *     W_SWEEP    tot0 = M^T (M (x0 + x1)) over the lower triangle (x1 may be NULL), IdentRowOp.
+ *   cols (second stage of PRE_ACC / ITER_*): REDUCE: tot0 / tot1 = the totals (reduce_cols, StoreColOp; padding columns
+ *   zero); PRE: pre_cols_kernel with both partial sets, PRE_ONE: with the second set absent (the only one of the two a
+ *   lean pass may take): g (g_h .. g_e), x_cur, xt, zt_scale = zs, rho, alpha -> x12, xtemp, rhs (n_pad entries
+ *   written) and col_scalars[0..4); PACK: pack (2 n_pad + 6 doubles) = both totals as doubles, then scalars[0..6) as
+ *   the extra workgroup of pack_cols_kernel sums them (not for ITER_LEAN).
+ *   Scalar partials are added by launch_sum_jobs with the strides and offsets the iteration uses.
+ *   Vectors: every row-side array (ycur, y12, yt, ytemp, ynew, y12s, ytemps, f_*) has row_len >= rows elements, every
+ *   column-side one (x0, x1, tot0, tot1, x_cur, xt, x12, xtemp, rhs, g_*) col_len >= n_pad; dots (may be NULL) has
+ *   2 row_len: M x0 and M x1 (W_SWEEP: M (x0 + x1) over the triangle, once) by the solver's plain row-dot launch.  An
+ *   array a form does not use may be NULL.  Output arrays are uploaded before and downloaded after the launches, so what
+ *   a launch does not write comes back as it was.  The device's partial-sum buffers start as NaN.
+ *   info (8 ints) = {tpb, nv, rows per workgroup step, grid of the pass, windows, kernel (0 plain, 1 triangular,
+ *   2 prefetching), partial sets' count handed to the second stage, 1 if windowed}.
+ * Invalid arguments are refused before any device work: POGS_ERROR, and PogsAmdLastError names the argument. */
+enum { POGS_AMD_PASS_PRE_ACC = 0, POGS_AMD_PASS_ITER_FULL = 1, POGS_AMD_PASS_ITER_LEAN = 2, POGS_AMD_PASS_EXACT = 3,
+       POGS_AMD_PASS_W_SWEEP = 4 };
+enum { POGS_AMD_PASS_FN_CHEAP = 0, POGS_AMD_PASS_FN_LOGISTIC = 1, POGS_AMD_PASS_FN_XSIDE = 2 };
+enum { POGS_AMD_PASS_COLS_REDUCE = 0, POGS_AMD_PASS_COLS_PRE = 1, POGS_AMD_PASS_COLS_PRE_ONE = 2,
+       POGS_AMD_PASS_COLS_PACK = 3 };
+typedef struct PogsAmdDensePassArgs {
+  int dtype, form, functor, cols;
+  int rows, n;
+  const void *M;
+  size_t ldm;
+  int num_cu, force_tpb, force_nv;
+  size_t row_len, col_len;
+  const void *x0, *x1;
+  const void *ycur, *y12, *yt;
+  void *ytemp;
+  const int *f_h;
+  const void *f_a, *f_b, *f_c, *f_d, *f_e;
+  double rho, alpha, zs, c_old;
+  void *ynew, *y12s, *ytemps, *dots;
+  double *scalars;       /* 6 */
+  void *tot0, *tot1;
+  double *pack;
+  const int *g_h;
+  const void *g_a, *g_b, *g_c, *g_d, *g_e;
+  const void *x_cur, *xt;
+  void *x12, *xtemp, *rhs;
+  double *col_scalars;   /* 4 */
+  int *info;             /* 8 */
+} PogsAmdDensePassArgs;
+int PogsAmdDensePassCheck(const PogsAmdDensePassArgs *args);
 /* The Norm2Est start vector (reference: gsl::rand, src/cpu/include/gsl/gsl_rand.h:8-16). */
 int PogsAmdRandUniform(int dtype, size_t n, void *out_host);
 

@@ -250,6 +250,7 @@ ABI_SYMBOLS = [
     "PogsAmdReadBandwidth", "PogsAmdWaveSumCheck", "PogsAmdBlockIdCheck", "PogsAmdBatchRowsCheck", "PogsAmdBatchColsCheck",
     "PogsAmdSpBatchSpmvCheck", "PogsAmdManySetupCheck", "PogsAmdGramCheck", "PogsAmdCholCheck",
     "PogsAmdSpmvCheck", "PogsAmdSparseCgCheck", "PogsAmdGetFactor", "PogsAmdSparseGramCheck", "PogsAmdTriMatvecCheck",
+    "PogsAmdDensePassCheck",
 ]
 
 
@@ -526,6 +527,108 @@ def tri_matvec_check(tri, M, x, y=None):
     if lib.PogsAmdTriMatvecCheck(code, int(tri), M.shape[0], M.ctypes.data, M.shape[1], x.ctypes.data, y.ctypes.data) != 0:
         raise RuntimeError(last_error())
     return y
+
+
+class PogsAmdDensePassArgs(ctypes.Structure):
+    """include/pogs_amd.h: the arguments of PogsAmdDensePassCheck."""
+    _fields_ = [("dtype", c_int), ("form", c_int), ("functor", c_int), ("cols", c_int), ("rows", c_int), ("n", c_int),
+                ("M", c_void_p), ("ldm", c_size_t), ("num_cu", c_int), ("force_tpb", c_int), ("force_nv", c_int),
+                ("row_len", c_size_t), ("col_len", c_size_t), ("x0", c_void_p), ("x1", c_void_p),
+                ("ycur", c_void_p), ("y12", c_void_p), ("yt", c_void_p), ("ytemp", c_void_p),
+                ("f_h", c_void_p), ("f_a", c_void_p), ("f_b", c_void_p), ("f_c", c_void_p), ("f_d", c_void_p), ("f_e", c_void_p),
+                ("rho", c_double), ("alpha", c_double), ("zs", c_double), ("c_old", c_double),
+                ("ynew", c_void_p), ("y12s", c_void_p), ("ytemps", c_void_p), ("dots", c_void_p), ("scalars", c_void_p),
+                ("tot0", c_void_p), ("tot1", c_void_p), ("pack", c_void_p),
+                ("g_h", c_void_p), ("g_a", c_void_p), ("g_b", c_void_p), ("g_c", c_void_p), ("g_d", c_void_p), ("g_e", c_void_p),
+                ("x_cur", c_void_p), ("xt", c_void_p), ("x12", c_void_p), ("xtemp", c_void_p), ("rhs", c_void_p),
+                ("col_scalars", c_void_p), ("info", c_void_p)]
+
+
+lib.PogsAmdDensePassCheck.argtypes = [ctypes.POINTER(PogsAmdDensePassArgs)]
+PASS_PRE_ACC, PASS_ITER_FULL, PASS_ITER_LEAN, PASS_EXACT, PASS_W_SWEEP = range(5)   # `form` of PogsAmdDensePassCheck
+PASS_FN_CHEAP, PASS_FN_LOGISTIC, PASS_FN_XSIDE = range(3)                           # `functor`
+PASS_COLS_REDUCE, PASS_COLS_PRE, PASS_COLS_PRE_ONE, PASS_COLS_PACK = range(4)       # `cols`
+PASS_INFO = ("tpb", "nv", "rows_per_step", "grid", "windows", "kernel", "nparts", "xl")
+PASS_KERNEL_PLAIN, PASS_KERNEL_TRI, PASS_KERNEL_PF = range(3)
+PASS_ROW_VECTORS = ("ycur", "y12", "yt", "ytemp", "ynew", "y12s", "ytemps")
+PASS_COL_VECTORS = ("x0", "x1", "tot0", "tot1", "x_cur", "xt", "x12", "xtemp", "rhs")
+PASS_OUTPUTS = ("ytemp", "ynew", "y12s", "ytemps", "dots", "tot0", "tot1", "pack", "x12", "xtemp", "rhs")
+
+
+def dense_pass_check(form, M, n, vec, functor=PASS_FN_CHEAP, cols=PASS_COLS_REDUCE, f=None, g=None, rho=1.0, alpha=1.0,
+                     zs=1.0, c_old=0.0, num_cu=0, force=None):
+    """One dense streaming pass and its second stage by the solver's own kernels (include/pogs_amd.h:
+    PogsAmdDensePassCheck).  M: rows x ldm; vec: dict of the vectors the form uses, by the names of the C struct
+    (PASS_ROW_VECTORS of one length >= rows, PASS_COL_VECTORS of one length >= n_pad, "dots" of twice the row length,
+    "pack" of 2 n_pad + 6 doubles); f / g: dicts of h, a .. e of the row / column length; force: (tpb, nv) or None.
+    Returns a dict: copies of the arrays of PASS_OUTPUTS that were given, as the launches left them, "scalars" (6),
+    "col_scalars" (4) and "info" (dict of PASS_INFO).  The arrays of vec are not changed."""
+    import numpy as np
+    M = np.ascontiguousarray(M)
+    if M.ndim != 2:
+        raise ValueError("M (rows, ldm)")
+    unknown = set(vec) - set(PASS_ROW_VECTORS) - set(PASS_COL_VECTORS) - {"dots", "pack"}
+    if unknown:
+        raise ValueError("unknown vectors: %s" % sorted(unknown))
+    arrs = {k: (np.array(v, order="C", copy=True) if k in PASS_OUTPUTS else np.ascontiguousarray(v))
+            for k, v in vec.items() if v is not None}
+    typed = [v for k, v in arrs.items() if k != "pack"]
+    for fn in (f, g):
+        if fn is not None:
+            typed += [np.ascontiguousarray(fn[k]) for k in "abcde"]
+    code = _dtype_code(M, *typed)
+    if "pack" in arrs and arrs["pack"].dtype != np.float64:
+        raise ValueError("pack: float64")
+    vecw = 4 if code == 0 else 2
+    n_pad = -(-int(n) // vecw) * vecw
+
+    def one_length(names, fn, what, least):
+        lens = {arrs[k].size for k in names if k in arrs}
+        if fn is not None:
+            lens |= {np.asarray(fn[k]).size for k in "habcde"}
+        if len(lens) > 1 or any(v.ndim != 1 for k, v in arrs.items() if k in names):
+            raise ValueError("%s-side vectors: one length, one dimension" % what)
+        ln = lens.pop() if lens else least
+        if ln < least:
+            raise ValueError("%s-side vectors: at least %d elements" % (what, least))
+        return ln
+
+    row_len = one_length(PASS_ROW_VECTORS, f, "row", M.shape[0])
+    col_len = one_length(PASS_COL_VECTORS, g, "column", n_pad)
+    if "dots" in arrs and f is None and not set(arrs) & set(PASS_ROW_VECTORS):   # (W_SWEEP: dots alone sets the row length)
+        row_len = max(row_len, arrs["dots"].size // 2)
+    if "dots" in arrs and arrs["dots"].size != 2 * row_len:
+        raise ValueError("dots: twice the row length")
+    if "pack" in arrs and arrs["pack"].size != 2 * n_pad + 6:
+        raise ValueError("pack: 2 n_pad + 6 doubles")
+    a = PogsAmdDensePassArgs()
+    a.dtype, a.form, a.functor, a.cols = code, int(form), int(functor), int(cols)
+    a.rows, a.n, a.M, a.ldm = M.shape[0], int(n), M.ctypes.data, M.shape[1]
+    a.num_cu = int(num_cu)
+    a.force_tpb, a.force_nv = (0, 0) if force is None else (int(force[0]), int(force[1]))
+    a.row_len, a.col_len = row_len, col_len
+    for k, v in arrs.items():
+        setattr(a, k, v.ctypes.data)
+    keep = []
+    for fn, pre in ((f, "f_"), (g, "g_")):
+        if fn is None:
+            continue
+        h = np.ascontiguousarray(fn["h"], dtype=np.int32)
+        keep.append(h)
+        setattr(a, pre + "h", h.ctypes.data)
+        for k in "abcde":
+            c = np.ascontiguousarray(fn[k])
+            keep.append(c)
+            setattr(a, pre + k, c.ctypes.data)
+    a.rho, a.alpha, a.zs, a.c_old = float(rho), float(alpha), float(zs), float(c_old)
+    scalars, col_scalars = np.full(6, np.nan), np.full(4, np.nan)
+    info = np.zeros(8, dtype=np.int32)
+    a.scalars, a.col_scalars, a.info = scalars.ctypes.data, col_scalars.ctypes.data, info.ctypes.data
+    if lib.PogsAmdDensePassCheck(ctypes.byref(a)) != 0:
+        raise RuntimeError(last_error())
+    out = {k: arrs[k] for k in PASS_OUTPUTS if k in arrs}
+    out.update(scalars=scalars, col_scalars=col_scalars, info=dict(zip(PASS_INFO, (int(v) for v in info))))
+    return out
 
 
 def get_factor(handle, k, dtype):

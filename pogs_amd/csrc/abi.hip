@@ -8,6 +8,7 @@
 #include "engine.h"
 #include "factor_check.h"
 #include "many_kernels.h"
+#include "pass_check.h"
 #include "sparse_batch_kernels.h"
 #include "sparse_direct.h"
 #include "spmv_check.h"
@@ -26,11 +27,15 @@ static_assert(kTriLower == kLower && kTriUpper == kUpper, "sparse_direct.h resta
   SolverBase *make_dense_solver_f32_p##TPB_##_##NV_(int, size_t, size_t, const void *, int, const PogsAmdOptions *, \
                                                     const PogsAmdDist *);                                          \
   SolverBase *make_dense_solver_f64_p##TPB_##_##NV_(int, size_t, size_t, const void *, int, const PogsAmdOptions *, \
-                                                    const PogsAmdDist *);
+                                                    const PogsAmdDist *);                                          \
+  void dense_pass_check_f32_p##TPB_##_##NV_(const PogsAmdDensePassArgs *, int);                                    \
+  void dense_pass_check_f64_p##TPB_##_##NV_(const PogsAmdDensePassArgs *, int);
 POGS_STREAM_PLANS(POGS_DECLARE_PLAN)
 #undef POGS_DECLARE_PLAN
 SolverBase *make_dense_solver_f32_xl(int, size_t, size_t, const void *, int, const PogsAmdOptions *, const PogsAmdDist *);
 SolverBase *make_dense_solver_f64_xl(int, size_t, size_t, const void *, int, const PogsAmdOptions *, const PogsAmdDist *);
+void dense_pass_check_f32_xl(const PogsAmdDensePassArgs *, int);
+void dense_pass_check_f64_xl(const PogsAmdDensePassArgs *, int);
 
 template <typename T>
 inline StreamPlan dense_plan_for(size_t m, size_t n, const PogsAmdOptions *opt, const PogsAmdDist *dist) {
@@ -57,6 +62,29 @@ inline SolverBase *make_dense_solver(int dtype, int ord, size_t m, size_t n, con
   POGS_STREAM_PLANS(POGS_PICK_PLAN)
 #undef POGS_PICK_PLAN
   throw Error("no dense solver for this streaming shape");
+}
+
+// PogsAmdDensePassCheck: refusals first (no device), then the object of the shape, as make_dense_solver picks it
+inline void dense_pass_check(const PogsAmdDensePassArgs *a) {
+  POGS_CHECK(a != nullptr, "null argument: args");
+  pass_check_validate(*a);
+  int num_cu = a->num_cu;
+  if (num_cu == 0) {
+    int dev = 0;
+    hipDeviceProp_t prop;
+    POGS_HIP_CHECK(hipGetDevice(&dev));
+    POGS_HIP_CHECK(hipGetDeviceProperties(&prop, dev));
+    num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+  }
+  const bool f32 = a->dtype == POGS_AMD_F32;
+  const StreamPlan p = f32 ? pass_check_plan<float>(*a, num_cu) : pass_check_plan<double>(*a, num_cu);
+  if (p.xl) return f32 ? dense_pass_check_f32_xl(a, num_cu) : dense_pass_check_f64_xl(a, num_cu);
+#define POGS_PICK_PLAN(TPB_, NV_)                                                          \
+  if (p.tpb == TPB_ && p.nv == NV_)                                                        \
+    return f32 ? dense_pass_check_f32_p##TPB_##_##NV_(a, num_cu) : dense_pass_check_f64_p##TPB_##_##NV_(a, num_cu);
+  POGS_STREAM_PLANS(POGS_PICK_PLAN)
+#undef POGS_PICK_PLAN
+  throw Error("no dense pass check for this streaming shape");
 }
 SolverBase *make_sparse_solver(int dtype, int ord, size_t m, size_t n, size_t nnz, const void *data,
                                const int *ptr, const int *ind, int mem, const PogsAmdOptions *opt,
@@ -739,6 +767,13 @@ int PogsAmdGramCheck(int dtype, int kdim, int k, const void *P, size_t lda, int 
       gram_check<float>(kdim, k, static_cast<const float *>(P), lda, num_cu, force, static_cast<float *>(G), ldg, info);
     else
       gram_check<double>(kdim, k, static_cast<const double *>(P), lda, num_cu, force, static_cast<double *>(G), ldg, info);
+    return 0;
+  });
+}
+
+int PogsAmdDensePassCheck(const PogsAmdDensePassArgs *args) {
+  return guarded([&]() {
+    dense_pass_check(args);
     return 0;
   });
 }

@@ -20,6 +20,7 @@
 #pragma once
 #include <atomic>
 #include <cstdlib>
+#include <type_traits>
 #include <hip/hip_runtime.h>
 
 #include "common.h"
@@ -136,6 +137,24 @@ constexpr int stream2_waves_per_simd(int tpb, int nv, int nd = 2, int na = 2) {
   return (stream2_blocks_per_cu(tpb, nv, nd, na) * (tpb / 64) + 3) / 4;
 }
 
+// The plan of one plain (not windowed) shape of POGS_STREAM_PLANS on num_cu CUs: its grids.
+inline StreamPlan stream_plan_of_shape(int tpb, int nv, int num_cu) {
+  StreamPlan p;
+  p.tpb = tpb; p.nv = nv; p.ok = true;
+  if (tpb == 64) {
+    p.grid_max = p.grid_dot = num_cu * 8;
+  } else if (tpb == 256) {
+    p.grid_dot = num_cu * 2;
+    // at nv = 5 the one-pass iteration kernel takes two rows per step (stream2_rows_c), needs 167
+    // VGPRs and fits three workgroups per CU: a slow row functor (logistic prox) hides better
+    p.num_cu = num_cu;
+    p.grid_max = num_cu * std::max(stream2_blocks_per_cu(256, nv), stream2_blocks_per_cu(256, nv, 1, 1));   // (nv <= 2: 8 rows per step, 158 VGPRs; 500000 x 2000: 0.694 -> 0.657 ms)
+  } else {
+    p.grid_max = p.grid_dot = num_cu;
+  }
+  return p;
+}
+
 // Chooses the workgroup shape for rows of n_pad elements.
 template <typename T>
 inline StreamPlan make_stream_plan(int n_pad, int num_cu) {
@@ -152,19 +171,11 @@ inline StreamPlan make_stream_plan(int n_pad, int num_cu) {
   const char *xl_env = std::getenv("POGS_AMD_XL_LIMIT");
   const bool forced_xl = xl_env && vpr > std::atoi(xl_env);
   for (int nv : nv64)
-    if (!forced_xl && vpr <= 64 * nv) { p.tpb = 64; p.nv = nv; p.grid_max = p.grid_dot = num_cu * 8; p.ok = true; return p; }
+    if (!forced_xl && vpr <= 64 * nv) return stream_plan_of_shape(64, nv, num_cu);
   for (int nv : nv256)
-    if (!forced_xl && vpr <= 256 * nv) {
-      p.tpb = 256; p.nv = nv; p.grid_dot = num_cu * 2;
-      // at nv = 5 the one-pass iteration kernel takes two rows per step (stream2_rows_c), needs 167
-      // VGPRs and fits three workgroups per CU: a slow row functor (logistic prox) hides better
-      p.num_cu = num_cu;
-      p.grid_max = num_cu * std::max(stream2_blocks_per_cu(256, nv), stream2_blocks_per_cu(256, nv, 1, 1));   // (nv <= 2: 8 rows per step, 158 VGPRs; 500000 x 2000: 0.694 -> 0.657 ms)
-      p.ok = true;
-      return p;
-    }
+    if (!forced_xl && vpr <= 256 * nv) return stream_plan_of_shape(256, nv, num_cu);
   for (int nv : nv512)
-    if (!forced_xl && vpr <= 512 * nv) { p.tpb = 512; p.nv = nv; p.grid_max = p.grid_dot = num_cu; p.ok = true; return p; }
+    if (!forced_xl && vpr <= 512 * nv) return stream_plan_of_shape(512, nv, num_cu);
   // POGS_AMD_XL_LIMIT=<vectors> (testing aid): rows wider than that take the windowed form below,
   // with small windows so that small test matrices span several of them
   int limit = 1024 * 8;
@@ -172,7 +183,7 @@ inline StreamPlan make_stream_plan(int n_pad, int num_cu) {
   if (const char *ev = std::getenv("POGS_AMD_XL_LIMIT")) { limit = std::atoi(ev); small_windows = true; }
   if (vpr <= limit) {
     for (int nv : nv1024)
-      if (vpr <= 1024 * nv) { p.tpb = 1024; p.nv = nv; p.grid_max = p.grid_dot = num_cu; p.ok = true; return p; }
+      if (vpr <= 1024 * nv) return stream_plan_of_shape(1024, nv, num_cu);
   }
   p.xl = true;
   p.ok = true;
@@ -969,6 +980,20 @@ __global__ void __launch_bounds__(TPB, (2 * (TPB / 64) + 3) / 4) stream_rows2_pf
       for (int k = 0; k < NS; ++k) a.scalar_partials[static_cast<size_t>(bid) * NS + k] = sacc[k];
     }
   }
+}
+
+// The per-solve tuning of the one-pass kernel at 256 x 5 in fp32 (StreamPlan::bpc_override, StreamPlan::pf), from what
+// the solve's functions allow: fused = the one-pass iteration runs, logistic = with the inlined logistic prox,
+// tmode = on the transposed storage (m <= n).  One function for the solver (dense_iter.h: load_problem) and for
+// PogsAmdDensePassCheck (pass_check.h), so that the check launches what a solve launches.
+#ifndef POGS_NV5_CHEAP_BPC   // (0: three per CU for every solve at 256 x 5, as before round 6 -- A / B builds)
+#define POGS_NV5_CHEAP_BPC 2
+#endif
+template <typename T>
+inline void tune_stream_plan(StreamPlan &p, bool fused, bool logistic, bool tmode) {
+  const bool nv5 = std::is_same<T, float>::value && p.tpb == 256 && p.nv == 5;
+  p.bpc_override = (POGS_NV5_CHEAP_BPC > 0 && fused && !logistic && !tmode && nv5) ? POGS_NV5_CHEAP_BPC : 0;
+  p.pf = POGS_NV5_PREFETCH != 0 && logistic && !tmode && nv5;
 }
 
 // Whether the two-dot / two-accumulator kernel fits the register file for this plan
