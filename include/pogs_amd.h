@@ -104,7 +104,9 @@ enum POGS_AMD_DTYPE { POGS_AMD_F32 = 0, POGS_AMD_F64 = 1 };
 enum POGS_AMD_MEM { POGS_AMD_HOST = 0, POGS_AMD_DEVICE = 1 };
 enum POGS_AMD_PROJECTOR { POGS_AMD_PROJ_DEFAULT = 0, /* dense: direct; sparse: CGLS by default, DIRECT for
                                                         min(m, n) <= POGS_AMD_SPARSE_DIRECT_MAX, one GPU */
-                          POGS_AMD_PROJ_DIRECT = 1, POGS_AMD_PROJ_CGLS = 2 };
+                          POGS_AMD_PROJ_DIRECT = 1, POGS_AMD_PROJ_CGLS = 2,
+                          POGS_AMD_PROJ_CGLS_FUSED = 3 /* dense, one GPU: CGLS with one pass over A per CG step and
+                                                          one host poll per ADMM iteration (PogsAmdCreateDense) */ };
 /* largest min(m, n) of a sparse handle with the direct projector (its factor is two dense K x K matrices) */
 #define POGS_AMD_SPARSE_DIRECT_MAX 16384
 
@@ -173,7 +175,19 @@ int PogsAmdDistUniqueId(char *out);
  * equilibrated (reference: src/cpu/matrix/matrix_dense.cpp:116-200), its norm
  * estimated (src/cpu/include/equil_helper.h:107-135) and the projector set up
  * (src/cpu/projector/projector_direct_dense.cpp:45-84,116-121).  With dist,
- * m is the LOCAL row count. */
+ * m is the LOCAL row count.
+ * opt->projector: DEFAULT and DIRECT factor the Gram matrix.  CGLS (one GPU, any shape) builds no factor and runs the
+ * reference's CGLS loop (projector_cgls.cpp:52-88): two passes over A and one host poll per CG step.
+ * CGLS_FUSED (one GPU, any shape, both types, both orderings, host or device A) stores A and estimates the norm as
+ * CGLS does, builds no factor, and runs the same arithmetic as a device-resident loop: q = A p and the column sums of
+ * A^T q come from ONE pass over A, s = A^T r - x is kept by the recurrence s -= alpha (A^T q + p) inside a projection
+ * (formed explicitly at its start), and the host polls once per ADMM iteration (csrc/dense_cg_fused.h).  y = A x comes
+ * from the recurrence y_warm + sum alpha q, and from the product every POGS_AMD_YSYNC-th iteration (default 16).
+ * stats: matvecs counts the launches that read A (per projection 1 + the CG steps; a row wider than one register
+ * tile is read twice per step), cg_iters the CG steps.  Every sum has one fixed order: two runs give the same bytes.
+ * With dist->world > 1 both CGLS values are refused.  On a handle of either CGLS value PogsAmdSolveBatchFn,
+ * PogsAmdSolveBatchWarmFn and PogsAmdGetFactor return POGS_ERROR and the handle stays usable.  PogsAmdCreateSparse
+ * refuses CGLS_FUSED before anything is built. */
 int PogsAmdCreateDense(PogsAmdSolver **out, int dtype, enum ORD ord, size_t m,
                        size_t n, const void *A, int mem,
                        const PogsAmdOptions *opt, const PogsAmdDist *dist);
@@ -573,6 +587,23 @@ int PogsAmdSparseCgCheck(PogsAmdSolver *s, const void *x0, const void *y0, const
                          const void *x_prev, const void *x12, const void *y12, double tol, int max_steps, int ahead,
                          int ysync, int loop, void *x, void *y_new, void *xtemp, void *ytemp, void *r, void *p, void *sv,
                          double *slots, double *rec_x, int *info, int *enqueued);
+/* Diagnostic of the dense fused CGLS projector: one projection on given vectors, on a live handle created with
+ * POGS_AMD_PROJ_CGLS_FUSED, by the member an ADMM iteration calls, without the prox step.  HOST arrays of the handle's
+ * type; n-sized: x0, x_warm, x, p, sv; m-sized: y0, y_warm, y_new, r.  A is the handle's equilibrated matrix
+ * (PogsAmdGetEquil).  The projection of (x0, y0) onto {y = A x} is started from x_warm, and y_warm stands for A x_warm.
+ * The entry puts r = y0 - y_warm and x = x_warm - x0 in place as the prox launch leaves them, clears the done flag and
+ * the step count, and runs the loop with `ahead` (>= 1) steps enqueued before the first host poll and at most
+ * max_steps (>= 1; a solve: 500) in all, then the closing launch (x += x0).  ysync = 0: y_new = y_warm + sum alpha q;
+ * 1: y_new = A x by the product.  tol: the relative tolerance of cgls.h:301-305.  Outputs: x, y_new; the loop's r, p,
+ * s (sv); slots (17 doubles) as PogsAmdSparseCgCheck returns them; *enqueued: the steps the host enqueued; *steps: the
+ * steps the loop took; *matvecs: the launches that read A (what the call added to stats.matvecs).
+ * POGS_ERROR, before any device work: a null argument, ahead < 1, max_steps < 1, ysync out of range, any other kind of
+ * handle.  The handle solves afterwards as if the call had not been made (its step prediction and its statistics are
+ * put back); a run begun with PogsAmdBeginRun is lost, PogsAmdIterate is refused until the next PogsAmdBeginRun /
+ * PogsAmdSolve. */
+int PogsAmdDenseCgCheck(PogsAmdSolver *s, const void *x0, const void *y0, const void *x_warm, const void *y_warm,
+                        double tol, int max_steps, int ahead, int ysync, void *x, void *y_new, void *r, void *p, void *sv,
+                        double *slots, int *enqueued, int *steps, unsigned long long *matvecs);
 /* W = L^-1 and U = W^T of a handle with the direct projector (dense, or sparse created with POGS_AMD_PROJ_DIRECT),
  * L L^T = I + A_eq^T A_eq (m > n) or I + A_eq A_eq^T: HOST outputs of k x k, k = min(m, n), either may be NULL.  On
  * row shards every rank holds the factor of the whole matrix.  POGS_ERROR on a handle that runs the CGLS projector

@@ -53,6 +53,7 @@ F32, F64 = 0, 1
 HOST, DEVICE = 0, 1
 COL_MAJ, ROW_MAJ = 0, 1
 PROJ_DEFAULT, PROJ_DIRECT, PROJ_CGLS = 0, 1, 2
+PROJ_CGLS_FUSED = 3   # dense, one GPU: one pass over A per CG step, one host poll per iteration
 
 
 class PogsAmdDist(ctypes.Structure):
@@ -193,6 +194,7 @@ lib.PogsAmdSpmvCheck.argtypes = [c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                  c_double, c_char, c_int, c_double, c_double, c_double, c_void_p, c_size_t, c_void_p,
                                  c_size_t, ctypes.POINTER(c_double), c_void_p, c_void_p, c_void_p, c_void_p]
 lib.PogsAmdSparseCgCheck.argtypes = [c_void_p] + [c_void_p] * 7 + [c_double, c_int, c_int, c_int, c_int] + [c_void_p] * 11
+lib.PogsAmdDenseCgCheck.argtypes = [c_void_p] + [c_void_p] * 4 + [c_double, c_int, c_int, c_int] + [c_void_p] * 9
 lib.PogsAmdGetFactor.argtypes = [c_void_p, c_void_p, c_void_p]
 lib.PogsAmdSparseGramCheck.argtypes = [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
                                        c_size_t, c_void_p]
@@ -250,7 +252,7 @@ ABI_SYMBOLS = [
     "PogsAmdReadBandwidth", "PogsAmdWaveSumCheck", "PogsAmdBlockIdCheck", "PogsAmdBatchRowsCheck", "PogsAmdBatchColsCheck",
     "PogsAmdSpBatchSpmvCheck", "PogsAmdManySetupCheck", "PogsAmdGramCheck", "PogsAmdCholCheck",
     "PogsAmdSpmvCheck", "PogsAmdSparseCgCheck", "PogsAmdGetFactor", "PogsAmdSparseGramCheck", "PogsAmdTriMatvecCheck",
-    "PogsAmdDensePassCheck",
+    "PogsAmdDensePassCheck", "PogsAmdDenseCgCheck",
 ]
 
 
@@ -468,6 +470,29 @@ def sparse_cg_check(handle, x0, y0, x_warm, y_warm, x_prev, x12, y12, tol, max_s
     out.update(zip(CG_SLOTS, (float(v) for v in slots)))
     out["info"] = tuple(dict(zip(SPMV_INFO, (int(v) for v in info[8 * c:8 * c + 8]))) for c in range(2))
     out["enqueued"] = enq.value
+    return out
+
+
+def dense_cg_check(handle, x0, y0, x_warm, y_warm, tol, max_steps=500, ahead=1, ysync=False):
+    """One projection of a live PROJ_CGLS_FUSED handle's loop on given vectors (include/pogs_amd.h: PogsAmdDenseCgCheck).
+    Vectors of the handle's dtype: x0, x_warm of one length (n), y0, y_warm of another (m).  Returns a dict: x, y_new, r,
+    p, s (arrays), the scalars of CG_SLOTS (floats), enqueued, steps and matvecs."""
+    import numpy as np
+    xs = [np.ascontiguousarray(v) for v in (x0, x_warm)]
+    ys = [np.ascontiguousarray(v) for v in (y0, y_warm)]
+    _dtype_code(*(xs + ys))
+    if any(v.ndim != 1 or v.size != xs[0].size for v in xs) or any(v.ndim != 1 or v.size != ys[0].size for v in ys):
+        raise ValueError("x0, x_warm of one length, y0, y_warm of another")
+    dt, n, m = xs[0].dtype, xs[0].size, ys[0].size
+    out = dict(x=np.empty(n, dt), y_new=np.empty(m, dt), r=np.empty(m, dt), p=np.empty(n, dt), s=np.empty(n, dt))
+    slots, enq, steps, mv = np.zeros(len(CG_SLOTS), np.float64), c_int(0), c_int(0), ctypes.c_ulonglong(0)
+    if lib.PogsAmdDenseCgCheck(handle, xs[0].ctypes.data, ys[0].ctypes.data, xs[1].ctypes.data, ys[1].ctypes.data, tol,
+                               int(max_steps), int(ahead), int(bool(ysync)),
+                               *(out[k].ctypes.data for k in ("x", "y_new", "r", "p", "s")), slots.ctypes.data,
+                               ctypes.addressof(enq), ctypes.addressof(steps), ctypes.addressof(mv)) != 0:
+        raise RuntimeError(last_error())
+    out.update(zip(CG_SLOTS, (float(v) for v in slots)))
+    out["enqueued"], out["steps"], out["matvecs"] = enq.value, steps.value, mv.value
     return out
 
 

@@ -42,7 +42,7 @@ inline StreamPlan dense_plan_for(size_t m, size_t n, const PogsAmdOptions *opt, 
   // the stored row length, as DenseSolver's constructor derives it
   const size_t m_global = (dist && dist->world >= 1) ? dist->m_global : m;
   const bool tall = m_global > n;
-  const bool cgls = opt && opt->projector == POGS_AMD_PROJ_CGLS;
+  const bool cgls = opt && (opt->projector == POGS_AMD_PROJ_CGLS || opt->projector == POGS_AMD_PROJ_CGLS_FUSED);
   const size_t stored_cols = (!tall && !cgls) ? m : n;
   return make_stream_plan<T>(static_cast<int>(round_up(stored_cols, Vec16<T>::N)), 256);
 }
@@ -341,6 +341,9 @@ int PogsAmdCreateSparse(PogsAmdSolver **out, int dtype, enum ORD ord, size_t m, 
                         const PogsAmdDist *dist) {
   return guarded([&]() {
     *out = nullptr;
+    // refused before anything is built: the sparse CGLS loop already is device-resident with one pass per product
+    POGS_CHECK(!(opt && opt->projector == POGS_AMD_PROJ_CGLS_FUSED),
+               "POGS_AMD_PROJ_CGLS_FUSED is a dense projector (a sparse handle: POGS_AMD_PROJ_CGLS runs the device-resident loop)");
     DeviceGuard guard(opt ? opt->device : -1);
     std::unique_ptr<PogsAmdSolver> h(new PogsAmdSolver);
     h->impl.reset(make_sparse_solver(dtype, ord, m, n, nnz, data, ptr, ind, mem, opt, dist));
@@ -821,6 +824,25 @@ int PogsAmdSparseCgCheck(PogsAmdSolver *s, const void *x0, const void *y0, const
     DeviceGuard guard(s->impl->device());
     s->impl->sparse_cg_check(SparseCgCheckArgs{x0, y0, x_warm, y_warm, x_prev, x12, y12, tol, max_steps, ahead, ysync, loop,
                                                x, y_new, xtemp, ytemp, r, p, sv, slots, rec_x, info, enqueued});
+    return 0;
+  });
+}
+
+int PogsAmdDenseCgCheck(PogsAmdSolver *s, const void *x0, const void *y0, const void *x_warm, const void *y_warm,
+                        double tol, int max_steps, int ahead, int ysync, void *x, void *y_new, void *r, void *p, void *sv,
+                        double *slots, int *enqueued, int *steps, unsigned long long *matvecs) {
+  return guarded([&]() {
+    // every refusal comes before the first HIP call (the handle's own: any handle but a dense fused one)
+    POGS_CHECK(x0 && y0 && x_warm && y_warm && x && y_new && r && p && sv && slots && enqueued && steps && matvecs,
+               "null argument");
+    POGS_CHECK(ysync == 0 || ysync == 1, "ysync must be 0 or 1");
+    POGS_CHECK(ahead >= 1, "ahead must be >= 1");
+    POGS_CHECK(max_steps >= 1, "max_steps must be >= 1");
+    POGS_CHECK(s && s->impl, "null solver");
+    if (!s->impl->has_dense_cg_fused()) throw Error("PogsAmdDenseCgCheck needs a dense handle created with POGS_AMD_PROJ_CGLS_FUSED");
+    DeviceGuard guard(s->impl->device());
+    s->impl->dense_cg_check(DenseCgCheckArgs{x0, y0, x_warm, y_warm, tol, max_steps, ahead, ysync, x, y_new, r, p, sv, slots,
+                                             enqueued, steps, matvecs});
     return 0;
   });
 }

@@ -94,13 +94,20 @@ bool DenseSolver<T, Tag>::iteration(unsigned verbose) {
   pa.rho = ctl_.rho; pa.alpha = ctl_.alpha(); pa.cheap = pre_cheap_;
   pa.partials = ctx_.spart.p;
   pa.blocks_x = pre_blocks(n_);
-  launch_admm_pre<T>(pa, s);
-  {
+  const double *S_fused = nullptr;
+  if (cg_fused_) {
+    // (1) + (2c) with the device-resident loop (dense_cg_fused.h): the prox launch starts the projection, the sums wait
+    // for the closing launch, one host poll
+    S_fused = prox_and_project_fused(pa, nw);
+  } else {
+    launch_admm_pre<T>(pa, s);
     SumJob j[2] = {{ctx_.spart.p, pa.blocks_x, 3, ctx_.S.p + kGapX},
                    {ctx_.spart.p + static_cast<size_t>(pa.blocks_x) * 3, pre_blocks(m_), 3, ctx_.S.p + kGapY}};
     launch_sum_jobs(j, 2, s);
   }
-  if (use_cgls_) {
+  if (cg_fused_) {
+    // (the projection ran with the prox step above)
+  } else if (use_cgls_) {
     // (2c) CGLS projector (projector_cgls.cpp:52-88), warm-started with the previous x (pogs.cpp:281)
     POGS_HIP_CHECK(hipMemcpyAsync(x_[nw].p, x_[cur_].p, n_ * sizeof(T), hipMemcpyDeviceToDevice, s));
     // y = A x (projector_cgls.cpp:78): from the CG recurrence y_warm + sum alpha_k q_k, except every
@@ -151,7 +158,7 @@ bool DenseSolver<T, Tag>::iteration(unsigned verbose) {
     t_mul_t(tmpn_.p, ProjTailColOp<T>{x_[nw].p, x_[cur_].p, x12_.p, xtemp_.p, n_}, ctx_.S.p + kDXprev2);
   }
   if (!use_cgls_) ctx_.stats.matvecs += 2;
-  const double *S = ctx_.fetch_scalars();
+  const double *S = S_fused ? S_fused : ctx_.fetch_scalars();
   ctl_.set_pre(S);
   bool exact = false;
   if (ctl_.set_approx(S, nrmA_)) {

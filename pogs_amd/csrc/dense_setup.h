@@ -85,6 +85,7 @@ void DenseSolver<T, Tag>::alloc_state() {
   if (use_cgls_) {
     cg_p_.alloc(np); cg_s_.alloc(np); cg_q_.alloc(m_); cg_r_.alloc(m_); cg_.alloc(kCgNumSlots);
     cg_p_.zero(s); cg_s_.zero(s); cg_.zero(s);
+    if (cg_fused_) alloc_cg_fused();
   }
   const char *fe = std::getenv("POGS_AMD_FUSED");
   fused_ok_ = (tall_ || tmode_) && !use_cgls_ && stream2_supported(planA_) && !(fe && fe[0] == '0');

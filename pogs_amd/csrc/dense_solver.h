@@ -24,6 +24,7 @@
 
 #include "batch_admm.h"
 #include "batch_kernels.h"
+#include "cg_fused.h"
 #include "cg_kernels.h"
 #include "engine.h"
 #include "fused_cols.h"
@@ -120,6 +121,9 @@ class DenseSolver final : public SolverBase {
           preload_gemm_code();
         });
     }
+    // refused before anything is built (no communicator is opened for a handle that cannot use it)
+    POGS_CHECK(!(opt && opt->projector == POGS_AMD_PROJ_CGLS_FUSED && dist && dist->world > 1),
+               "the CGLS projector is single-GPU (POGS_AMD_PROJ_CGLS_FUSED with row shards)");
     ctx_.init(opt ? opt->device : -1, opt ? opt->profile : 0);
     m_ = static_cast<int>(m);
     n_ = static_cast<int>(n);
@@ -135,7 +139,10 @@ class DenseSolver final : public SolverBase {
     POGS_CHECK(tall_ || !multi_, "row sharding needs m > n (SURVEY.md section 8(e))");
     // dense + CGLS: instantiated by the reference (pogs.cpp:1983-1984) but not reachable from
     // its C ABI; offered here as an option (no Gram / factorisation, any shape)
-    use_cgls_ = opt && opt->projector == POGS_AMD_PROJ_CGLS;
+    // POGS_AMD_PROJ_CGLS_FUSED: the same projector with the loop of dense_cg_fused.h (one pass over A per CG step, no
+    // host poll per step); everything outside the loop is shared
+    cg_fused_ = opt && opt->projector == POGS_AMD_PROJ_CGLS_FUSED;
+    use_cgls_ = cg_fused_ || (opt && opt->projector == POGS_AMD_PROJ_CGLS);
     if (const char *ys = std::getenv("POGS_AMD_YSYNC")) ysync_ = std::max(0, std::atoi(ys));
     POGS_CHECK(!(use_cgls_ && multi_), "the CGLS projector is single-GPU");
     constexpr int VEC = Vec16<T>::N;
@@ -202,7 +209,7 @@ class DenseSolver final : public SolverBase {
     if (p.verbose > 0 && ctx_.dist.rank() == 0) {
       print_summary(status, st.t_total_s, st.t_init_s, ctl_);
       if (p.verbose > 3) print_timing_breakdown(st.t_loop_s, st.iterations);
-      std::printf("POGS-AMD dense/%s: status %d, iter %u, init %.3e s, loop %.3e s\n", use_cgls_ ? "cgls" : "direct",
+      std::printf("POGS-AMD dense/%s: status %d, iter %u, init %.3e s, loop %.3e s\n", cg_fused_ ? "cgls-fused" : use_cgls_ ? "cgls" : "direct",
                   status, ctl_.k, st.t_init_s, st.t_loop_s);
     }
     return status;
@@ -283,8 +290,12 @@ class DenseSolver final : public SolverBase {
     POGS_HIP_CHECK(hipMemcpyAsync(xtemp_.p, x0, n_ * sizeof(T), hipMemcpyHostToDevice, s));
     POGS_HIP_CHECK(hipMemcpyAsync(ytemp_.p, y0, m_ * sizeof(T), hipMemcpyHostToDevice, s));
     if (use_cgls_) {
-      x_[0].zero(s);
-      cgls_project(xtemp_.p, ytemp_.p, x_[0].p, static_cast<T>(tol), nullptr);
+      if (cg_fused_) {
+        project_start_fused(tol);
+      } else {
+        x_[0].zero(s);
+        cgls_project(xtemp_.p, ytemp_.p, x_[0].p, static_cast<T>(tol), nullptr);
+      }
       StreamArgs<T> a = argsA();
       a.xin = x_[0].p;
       launch_stream<T, true, false, false, kFull, Tag>(planA_, a, GemvNOp<T>{1, 0, y_[0].p}, s);
@@ -308,6 +319,9 @@ class DenseSolver final : public SolverBase {
     POGS_HIP_CHECK(hipMemcpyAsync(y, y_[0].p, m_ * sizeof(T), hipMemcpyDeviceToHost, s));
     ctx_.sync();
   }
+
+  bool has_dense_cg_fused() const override { return cg_fused_; }
+  void dense_cg_check(const DenseCgCheckArgs &a) override;
 
   void mul(char trans, double alpha, const void *x, double beta, void *y) override {
     hipStream_t s = ctx_.stream;
@@ -506,6 +520,15 @@ class DenseSolver final : public SolverBase {
   // number of CG steps taken.
   int cgls_project(const T *x0, const T *y0, T *x, T tol, const T *Ax_warm, T *yacc = nullptr);
 
+  // ---- the one-pass, device-resident CGLS loop (POGS_AMD_PROJ_CGLS_FUSED; dense_cg_fused.h) ----
+  void alloc_cg_fused();
+  const double *cg_loop_fused(T *x, const T *xprev, const T *ycur, T *ynew, int ahead_steps, int max_steps, double tol,
+                              const double *pre_part, int *enqueued);
+  const double *project_cg_fused(int nw, bool ysync, int ahead, int max_steps, double tol, const double *pre_part,
+                                 int *enqueued);
+  const double *prox_and_project_fused(const AdmmPreArgs<T> &pa0, int nw);
+  void project_start_fused(double tol);
+
   // ---- per-solve -----------------------------------------------------------
   void load_problem(const FnHost &f, const FnHost &g, const SolveParams &p);
   FnView<T> fview() const { return FnView<T>{f_.h.p, fs_.a.p, f_.b.p, fs_.c.p, fs_.d.p, fs_.e.p}; }
@@ -561,6 +584,11 @@ class DenseSolver final : public SolverBase {
   DevBuf<T> x12s_, xtemps_;     // tmode_, one-pass iteration: speculative x12_{k+1}, xhat_{k+1}
   DevBuf<T> cg_p_, cg_s_, cg_q_, cg_r_;
   DevBuf<double> cg_;
+  bool cg_fused_ = false;       // POGS_AMD_PROJ_CGLS_FUSED (use_cgls_ is set too)
+  int cg_pred_ = 1;             // fused loop: CG steps enqueued ahead, what the previous projection took
+  DevBuf<double> cgf_rec_;      // fused loop: the per-block records and the partial sums of its launches
+  size_t cgo_q_ = 0, cgo_p_ = 0, cgo_x_ = 0, cgo_s_ = 0, cgo_s0_ = 0, cgo_pre_ = 0, cgo_close_ = 0;   // regions of cgf_rec_
+  std::vector<size_t> cgf_events_;   // fused loop: the timer brackets of the enqueued passes
   size_t lda_ = 0;
   StreamPlan planA_, planW_;
   const T *A_src_ = nullptr;    // upload() .. equilibrate(): the caller's device buffer standing in for A_
@@ -592,6 +620,7 @@ class DenseSolver final : public SolverBase {
 // the iterations for m > n, the m <= n mirror.
 #include "dense_setup.h"
 #include "dense_factor.h"
+#include "dense_cg_fused.h"
 #include "dense_iter.h"
 #include "dense_wide.h"
 #include "dense_batch.h"

@@ -701,6 +701,17 @@ struct SparseCgCheckArgs {
   int *enqueued;
 };
 
+// PogsAmdDenseCgCheck (include/pogs_amd.h, Part 3): HOST arrays of the handle's type, n- or m-sized as named there
+struct DenseCgCheckArgs {
+  const void *x0, *y0, *x_warm, *y_warm;
+  double tol;
+  int max_steps, ahead, ysync;
+  void *x, *y_new, *r, *p, *s;
+  double *slots;   // 17
+  int *enqueued, *steps;
+  unsigned long long *matvecs;
+};
+
 // Type-erased solver behind the C handle.
 struct SolverBase {
   virtual ~SolverBase() {}
@@ -730,6 +741,11 @@ struct SolverBase {
   virtual void project(const void *x0, const void *y0, double tol, void *x, void *y) = 0;
   // one projection of the sparse solver's CGLS loops on given vectors (one GPU)
   virtual void sparse_cg_check(const SparseCgCheckArgs &) { throw Error("PogsAmdSparseCgCheck needs a sparse handle"); }
+  // one projection of the dense solver's device-resident CGLS loop on given vectors (POGS_AMD_PROJ_CGLS_FUSED)
+  virtual bool has_dense_cg_fused() const { return false; }
+  virtual void dense_cg_check(const DenseCgCheckArgs &) {
+    throw Error("PogsAmdDenseCgCheck needs a dense handle created with POGS_AMD_PROJ_CGLS_FUSED");
+  }
   virtual void mul(char trans, double alpha, const void *x, double beta, void *y) = 0;
   virtual PogsAmdStats &stats() = 0;
   // guarded() in abi.hip: on_entry() when an entry point starts working on the handle, on_error()

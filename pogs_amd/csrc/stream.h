@@ -235,8 +235,19 @@ template <> __device__ __forceinline__ double2 vzero<double2>() { return make_do
 
 }  // namespace dev
 
+// A row functor of a device-resident loop (dense_cg_fused.h) declares `static constexpr bool kGuarded = true` and a
+// member skip(): its launch returns at once when skip() says that the loop has ended.  The guard exists only in the
+// kernels instantiated for such a functor (if constexpr); the code of every other instantiation is what it was.
+template <typename Op, typename = void>
+struct StreamOpGuarded : std::false_type {};
+template <typename Op>
+struct StreamOpGuarded<Op, std::enable_if_t<Op::kGuarded>> : std::true_type {};
+
 template <typename T, int TPB, int NV, int R, bool DOT, bool ACC, bool SQ, int TRI, typename Op>
 __global__ void __launch_bounds__(TPB) stream_rows_kernel(StreamArgs<T> a, Op op) {
+  if constexpr (StreamOpGuarded<Op>::value) {
+    if (op.skip()) return;
+  }
   using V = typename Vec16<T>::type;
   constexpr int VEC = Vec16<T>::N;
   constexpr int NW = TPB / 64;
@@ -538,11 +549,27 @@ struct XlVecUOp {       // column-sum coefficients from a vector
   __device__ __forceinline__ T row(int, T, double (&)[N]) const { return 0; }
   __device__ __forceinline__ T u(int i) const { return uvec[i]; }
 };
+// A window functor behind the guard of the pass's own functor (StreamOpGuarded): the window launches of a guarded
+// pass return with it.
+template <typename T, typename Inner, typename Op>
+struct XlGuardedOp {
+  static constexpr int NS = 0;
+  static constexpr bool kGuarded = true;
+  Inner in;
+  Op op;
+  __device__ __forceinline__ bool skip() const { return op.skip(); }
+  template <int N>
+  __device__ __forceinline__ T row(int i, T dot, double (&s)[N]) const { return in.row(i, dot, s); }
+  __device__ __forceinline__ T u(int i) const { return in.u(i); }
+};
 // dot_i = sum of the window partials (window order), then the row functor; its return value is
 // kept when a column-sum pass follows.  Scalar partials in the layout of the plain kernel.
 template <typename T, typename Op, bool KEEP_U>
 __global__ void __launch_bounds__(256) xl_apply_rows_kernel(const T *part, int m, int nwin, Op op, T *uvec,
                                                             double *scalar_partials) {
+  if constexpr (StreamOpGuarded<Op>::value) {
+    if (op.skip()) return;
+  }
   constexpr int NS = Op::NS > 0 ? Op::NS : 1;
   __shared__ double s_red[NS * 4];
   double sacc[NS];
@@ -621,8 +648,13 @@ void launch_stream(const StreamPlan &p, const StreamArgs<T> &a, const Op &op, hi
     const int gdot = stream_grid<true, false>(p, a.m);
     for (int c = 0; c < nwin; ++c) {
       aw.col0 = c * w;
-      launch_stream_window<T, true, false, SQ, TRI, Tag, XlStoreDotOp<T>>(p, aw, XlStoreDotOp<T>{part + static_cast<size_t>(c) * a.m},
-                                                                     s, gdot);
+      const XlStoreDotOp<T> dop{part + static_cast<size_t>(c) * a.m};
+      if constexpr (StreamOpGuarded<Op>::value) {
+        using G = XlGuardedOp<T, XlStoreDotOp<T>, Op>;
+        launch_stream_window<T, true, false, SQ, TRI, Tag, G>(p, aw, G{dop, op}, s, gdot);
+      } else {
+        launch_stream_window<T, true, false, SQ, TRI, Tag, XlStoreDotOp<T>>(p, aw, dop, s, gdot);
+      }
     }
     hipLaunchKernelGGL((xl_apply_rows_kernel<T, Op, ACC>), dim3(grid), dim3(256), 0, s, part, a.m, nwin, op, uvec,
                        a.scalar_partials);
@@ -630,8 +662,14 @@ void launch_stream(const StreamPlan &p, const StreamArgs<T> &a, const Op &op, hi
   if (ACC) {
     for (int c = 0; c < nwin; ++c) {
       aw.col0 = c * w;
-      if (DOT) launch_stream_window<T, false, true, SQ, TRI, Tag, XlVecUOp<T>>(p, aw, XlVecUOp<T>{uvec}, s, grid);
-      else launch_stream_window<T, false, true, SQ, TRI, Tag, Op>(p, aw, op, s, grid);
+      if constexpr (DOT && StreamOpGuarded<Op>::value) {
+        using G = XlGuardedOp<T, XlVecUOp<T>, Op>;
+        launch_stream_window<T, false, true, SQ, TRI, Tag, G>(p, aw, G{XlVecUOp<T>{uvec}, op}, s, grid);
+      } else if (DOT) {
+        launch_stream_window<T, false, true, SQ, TRI, Tag, XlVecUOp<T>>(p, aw, XlVecUOp<T>{uvec}, s, grid);
+      } else {
+        launch_stream_window<T, false, true, SQ, TRI, Tag, Op>(p, aw, op, s, grid);
+      }
     }
   }
 }

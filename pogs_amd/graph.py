@@ -532,7 +532,8 @@ class Solver:
     row-sharded solve where this process holds ``m`` consecutive rows.
     ``projector``: PROJ_DEFAULT (dense: direct, sparse: CGLS), PROJ_CGLS, or PROJ_DIRECT -- on a sparse matrix with
     min(m, n) <= SPARSE_DIRECT_MAX on one GPU the exact projector: two products and two triangular mat-vecs per
-    iteration instead of a CGLS loop (the one-shot ``solve_*`` calls keep CGLS).
+    iteration instead of a CGLS loop (the one-shot ``solve_*`` calls keep CGLS).  PROJ_CGLS_FUSED (dense, one GPU):
+    CGLS with one pass over A per CG step and one host poll per iteration (include/pogs_amd.h: PogsAmdCreateDense).
     """
 
     def __init__(self, A, dtype=None, shape=None, device_ptr=False, order=Ordering.ROW_MAJ, device=-1,
