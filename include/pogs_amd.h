@@ -694,6 +694,73 @@ typedef struct PogsAmdDensePassArgs {
   int *info;             /* 8 */
 } PogsAmdDensePassArgs;
 int PogsAmdDensePassCheck(const PogsAmdDensePassArgs *args);
+/* Diagnostic of the kernels that do not read the matrix (csrc/vec_kernels.hip) and of the scalar block's way to the host
+ * (csrc/engine.h: Ctx::queue_sum / fetch_scalars): ONE launch (plus the sum launch that follows it in a solve) on
+ * caller-supplied HOST arrays, through the launch functions and block-count helpers the solvers call.  Every x-side array
+ * (g_*, x_in[], x_out[]) has len_x >= n_x elements of dtype, every y-side one (f_*, y_in[], y_out[]) len_y >= n_y; every
+ * array given is uploaded before the launch and every output array downloaded after it, so what the launch does not
+ * write comes back as it was.  An array an op does not name may be NULL.  The device's partial-sum buffer starts as NaN
+ * (ops that write partials) and is returned whole in `partials` (partials_len doubles, at least what the op writes).
+ * `scalars` (64 doubles, in / out) is the device scalar block: slot numbers are those of csrc/vec_kernels.h (Slot).
+ * `s0`, `s1`, `rho`, `alpha`, `zs` are cast to dtype.  A sum job is 6 ints {first, nparts, ns, stride, offset, slot}:
+ * partial records start at partials[first], the ns sums go to scalars[slot ..].
+ *   SCALE_OBJECTIVE  launch_scale_objective: g, scale = x_in[0], mode 1 divide / 0 multiply; a, c, d, e -> x_out[0..4).
+ *   PROBE_UNIFORM    probe_uniform(g, n_x): info[0] = mask, info[1] = h; scalars[0..3) = c, d, e.
+ *   ADMM_PRE         launch_admm_pre: g, f; x_in = {x_cur, xt}, y_in = {y_cur, yt}; x_out = {x12, xtemp, x_aux or NULL},
+ *                    y_out likewise; cg (2 doubles, may be NULL) = cg_reset; cheap 0 / 1 as given (1 is refused when a
+ *                    function is outside is_cheap_prox); probe 1: ug / uf from probe_uniform, 0: from u_mask / u_h / u_cde
+ *                    ([0] g, [1] f).  partials = [pre_blocks(n_x) + pre_blocks(n_y)][3]; then launch_sum_jobs with the
+ *                    two jobs of the dense iteration: scalars[kGapX ..+3) and scalars[kGapY ..+3).
+ *                    info = {blocks_x, blocks_y, ug.mask, uf.mask}.
+ *   ADMM_TAIL        launch_admm_tail(n_x): x_in = {znew, zprev, z12}, x_out[0] = ztemp (in / out); partials
+ *                    [vec_blocks(n_x)][2], summed into scalars[kDXprev2 ..+2).  info[0] = blocks.
+ *   UNSCALE          launch_unscale: x_in = {x12, xt, xprev, e}, y_in = {y12, yt, yprev, d}; x_out = {x, mu or NULL},
+ *                    y_out = {y, l}.
+ *   EXACT_U          launch_exact_u(n_x): x_in = {y12, yt, yprev}, c = s0, u = x_out[0].
+ *   SCALE_BY         launch_scale_by: alpha = s0, x_in = {in, sc}, mode 1 divide / 0 multiply, x_out[0].
+ *   AXPBY            launch_axpby: a = s0, x = x_in[0], b = s1, y = x_out[0] (in / out).
+ *   SCAL, SQRT, FILL launch_scal (alpha = s0), launch_sqrt_inplace, launch_fill (v = s0) on x_out[0].
+ *   SUM_JOBS         launch_sum_jobs on the records in `partials` (input), njobs (1 .. 8) jobs.
+ *   MAX_PARTIALS     launch_max_partials(partials, partials_len) -> scalars[0].
+ *   SUM_CG           launch_sum_cg: jobs[0], scalars, cg (5 doubles, in / out), mode 1 / 2 / 3, shift = s0, eps = s1.
+ *   PUBLISH          on a context of the entry's own whose device block starts as `scalars`: njobs jobs are queued, the
+ *                    overlay (ov_src, ov_slot, ov_n; ov_src has ov_n[0] + ov_n[1] doubles) is set, fetch_scalars();
+ *                    then njobs2 jobs (jobs2) are queued and fetched with no overlay.  mode 0: the polling path, 1: the
+ *                    copying path (launch_apply_overlay, then a copy).  pub (4 x 64 doubles) = host block 1, device
+ *                    block 1, host block 2, device block 2; info = {counter word after fetch 1, after fetch 2,
+ *                    poll_fetch after fetch 1, after fetch 2}.
+ * Invalid arguments are refused before any device work: POGS_ERROR, and PogsAmdLastError names the argument. */
+enum { POGS_AMD_VEC_SCALE_OBJECTIVE = 0, POGS_AMD_VEC_PROBE_UNIFORM = 1, POGS_AMD_VEC_ADMM_PRE = 2,
+       POGS_AMD_VEC_ADMM_TAIL = 3, POGS_AMD_VEC_UNSCALE = 4, POGS_AMD_VEC_EXACT_U = 5, POGS_AMD_VEC_SCALE_BY = 6,
+       POGS_AMD_VEC_AXPBY = 7, POGS_AMD_VEC_SCAL = 8, POGS_AMD_VEC_SQRT = 9, POGS_AMD_VEC_FILL = 10,
+       POGS_AMD_VEC_SUM_JOBS = 11, POGS_AMD_VEC_MAX_PARTIALS = 12, POGS_AMD_VEC_SUM_CG = 13, POGS_AMD_VEC_PUBLISH = 14 };
+#define POGS_AMD_VEC_SCALARS 64
+typedef struct PogsAmdVecArgs {
+  int dtype, op, mode;
+  int n_x, n_y;
+  size_t len_x, len_y;
+  int cheap, probe;
+  int u_mask[2], u_h[2];
+  double u_cde[6];
+  double rho, alpha, zs, s0, s1;
+  const int *g_h;
+  const void *g_a, *g_b, *g_c, *g_d, *g_e;
+  const int *f_h;
+  const void *f_a, *f_b, *f_c, *f_d, *f_e;
+  const void *x_in[4], *y_in[4];
+  void *x_out[4], *y_out[4];
+  double *partials;
+  size_t partials_len;
+  const int *jobs, *jobs2;
+  int njobs, njobs2;
+  double *scalars;       /* 64 */
+  double *cg;            /* 5 (ADMM_PRE: 2) */
+  const double *ov_src;
+  int ov_slot[2], ov_n[2];
+  double *pub;           /* 4 x 64 */
+  int *info;             /* 4 */
+} PogsAmdVecArgs;
+int PogsAmdVecCheck(const PogsAmdVecArgs *args);
 /* The Norm2Est start vector (reference: gsl::rand, src/cpu/include/gsl/gsl_rand.h:8-16). */
 int PogsAmdRandUniform(int dtype, size_t n, void *out_host);
 

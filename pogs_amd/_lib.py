@@ -252,7 +252,7 @@ ABI_SYMBOLS = [
     "PogsAmdReadBandwidth", "PogsAmdWaveSumCheck", "PogsAmdBlockIdCheck", "PogsAmdBatchRowsCheck", "PogsAmdBatchColsCheck",
     "PogsAmdSpBatchSpmvCheck", "PogsAmdManySetupCheck", "PogsAmdGramCheck", "PogsAmdCholCheck",
     "PogsAmdSpmvCheck", "PogsAmdSparseCgCheck", "PogsAmdGetFactor", "PogsAmdSparseGramCheck", "PogsAmdTriMatvecCheck",
-    "PogsAmdDensePassCheck", "PogsAmdDenseCgCheck",
+    "PogsAmdDensePassCheck", "PogsAmdDenseCgCheck", "PogsAmdVecCheck",
 ]
 
 
@@ -654,6 +654,124 @@ def dense_pass_check(form, M, n, vec, functor=PASS_FN_CHEAP, cols=PASS_COLS_REDU
     out = {k: arrs[k] for k in PASS_OUTPUTS if k in arrs}
     out.update(scalars=scalars, col_scalars=col_scalars, info=dict(zip(PASS_INFO, (int(v) for v in info))))
     return out
+
+
+class PogsAmdVecArgs(ctypes.Structure):
+    """include/pogs_amd.h: the arguments of PogsAmdVecCheck."""
+    _fields_ = [("dtype", c_int), ("op", c_int), ("mode", c_int), ("n_x", c_int), ("n_y", c_int),
+                ("len_x", c_size_t), ("len_y", c_size_t), ("cheap", c_int), ("probe", c_int),
+                ("u_mask", c_int * 2), ("u_h", c_int * 2), ("u_cde", c_double * 6),
+                ("rho", c_double), ("alpha", c_double), ("zs", c_double), ("s0", c_double), ("s1", c_double),
+                ("g_h", c_void_p), ("g_a", c_void_p), ("g_b", c_void_p), ("g_c", c_void_p), ("g_d", c_void_p), ("g_e", c_void_p),
+                ("f_h", c_void_p), ("f_a", c_void_p), ("f_b", c_void_p), ("f_c", c_void_p), ("f_d", c_void_p), ("f_e", c_void_p),
+                ("x_in", c_void_p * 4), ("y_in", c_void_p * 4), ("x_out", c_void_p * 4), ("y_out", c_void_p * 4),
+                ("partials", c_void_p), ("partials_len", c_size_t), ("jobs", c_void_p), ("jobs2", c_void_p),
+                ("njobs", c_int), ("njobs2", c_int), ("scalars", c_void_p), ("cg", c_void_p), ("ov_src", c_void_p),
+                ("ov_slot", c_int * 2), ("ov_n", c_int * 2), ("pub", c_void_p), ("info", c_void_p)]
+
+
+lib.PogsAmdVecCheck.argtypes = [ctypes.POINTER(PogsAmdVecArgs)]
+VEC_OPS = ("SCALE_OBJECTIVE", "PROBE_UNIFORM", "ADMM_PRE", "ADMM_TAIL", "UNSCALE", "EXACT_U", "SCALE_BY", "AXPBY", "SCAL",
+           "SQRT", "FILL", "SUM_JOBS", "MAX_PARTIALS", "SUM_CG", "PUBLISH")          # `op` of PogsAmdVecCheck, in order
+(VEC_SCALE_OBJECTIVE, VEC_PROBE_UNIFORM, VEC_ADMM_PRE, VEC_ADMM_TAIL, VEC_UNSCALE, VEC_EXACT_U, VEC_SCALE_BY, VEC_AXPBY,
+ VEC_SCAL, VEC_SQRT, VEC_FILL, VEC_SUM_JOBS, VEC_MAX_PARTIALS, VEC_SUM_CG, VEC_PUBLISH) = range(15)
+VEC_SCALARS = 64     # include/pogs_amd.h: POGS_AMD_VEC_SCALARS
+# slot numbers of the device scalar block the entry sums into (csrc/vec_kernels.h: Slot)
+SLOT_GAP_Y, SLOT_GAP_X, SLOT_DXPREV2, SLOT_CG_Q2, SLOT_CG_P2, SLOT_CG_S2, NUM_SLOTS = 0, 12, 15, 9, 21, 22, 52
+
+
+def vec_check(op, dtype, n_x=0, n_y=0, x_in=(), y_in=(), x_out=(), y_out=(), g=None, f=None, mode=0, cheap=0, probe=0,
+              ug=None, uf=None, rho=1.0, alpha=1.0, zs=1.0, s0=0.0, s1=0.0, partials=None, jobs=None, jobs2=None,
+              scalars=None, cg=None, overlay=None):
+    """One launch of the element-wise kernels, or the scalar block's way to the host, by the solver's own launch
+    functions (include/pogs_amd.h: PogsAmdVecCheck).  x_in / x_out / y_in / y_out: sequences of arrays of `dtype` (None
+    for an absent optional one), each side of one length; g / f: dicts of h, a .. e; ug / uf: (mask, h, c, d, e);
+    partials, scalars (64), cg: float64; jobs / jobs2: rows of 6 ints {first, nparts, ns, stride, offset, slot};
+    overlay: (src, (slot0, slot1), (n0, n1)).  Returns a dict: copies of the output arrays as the launch left them
+    ("x_out", "y_out": lists), "partials", "scalars", "cg", "pub" (4 x 64, PUBLISH) and "info" (4 ints).  No argument is
+    changed."""
+    import numpy as np
+    dt = np.dtype(dtype)
+    if dt not in (np.float32, np.float64):
+        raise ValueError("dtype: float32 or float64")
+
+    def side(ins, outs, fn, what):
+        ins = [None if v is None else np.ascontiguousarray(v) for v in ins]
+        outs = [None if v is None else np.array(v, order="C", copy=True) for v in outs]
+        coef = {}
+        if fn is not None:
+            coef = {k: np.ascontiguousarray(fn[k]) for k in "abcde"}
+            coef["h"] = np.ascontiguousarray(fn["h"], dtype=np.int32)
+        typed = [v for v in ins + outs if v is not None] + [coef[k] for k in "abcde" if k in coef]
+        if any(v.dtype != dt for v in typed):
+            raise ValueError("%s-side arrays: one dtype, the one named" % what)
+        lens = {v.size for v in typed} | ({coef["h"].size} if coef else set())
+        if len(lens) > 1 or any(v.ndim != 1 for v in typed) or len(ins) > 4 or len(outs) > 4:
+            raise ValueError("%s-side arrays: one length, one dimension, at most four of a kind" % what)
+        return ins, outs, coef, (lens.pop() if lens else 0)
+
+    xi, xo, gc, len_x = side(x_in, x_out, g, "x")
+    yi, yo, fc, len_y = side(y_in, y_out, f, "y")
+    a = PogsAmdVecArgs()
+    a.dtype, a.op, a.mode = (0 if dt == np.float32 else 1), int(op), int(mode)
+    a.n_x, a.n_y, a.len_x, a.len_y = int(n_x), int(n_y), len_x, len_y
+    a.cheap, a.probe = int(cheap), int(probe)
+    for q, u in enumerate((ug, uf)):
+        if u is not None:
+            a.u_mask[q], a.u_h[q] = int(u[0]), int(u[1])
+            a.u_cde[3 * q], a.u_cde[3 * q + 1], a.u_cde[3 * q + 2] = float(u[2]), float(u[3]), float(u[4])
+    a.rho, a.alpha, a.zs, a.s0, a.s1 = float(rho), float(alpha), float(zs), float(s0), float(s1)
+    for pre, coef in (("g_", gc), ("f_", fc)):
+        for k, v in coef.items():
+            setattr(a, pre + k, v.ctypes.data)
+    for name, arrs in (("x_in", xi), ("x_out", xo), ("y_in", yi), ("y_out", yo)):
+        for k, v in enumerate(arrs):
+            if v is not None:
+                getattr(a, name)[k] = v.ctypes.data
+
+    def f64(v, what, size=None):
+        if v is None:
+            return None
+        v = np.array(v, order="C", copy=True)
+        if v.dtype != np.float64 or v.ndim != 1 or (size is not None and v.size != size):
+            raise ValueError("%s: float64, one dimension%s" % (what, "" if size is None else ", %d long" % size))
+        return v
+
+    def jobrows(v, what):
+        if v is None:
+            return None
+        v = np.ascontiguousarray(v, dtype=np.int32)
+        if v.ndim != 2 or v.shape[1] != 6:
+            raise ValueError("%s: rows of 6 ints" % what)
+        return v
+
+    partials, cg = f64(partials, "partials"), f64(cg, "cg")
+    scalars = np.full(VEC_SCALARS, np.nan) if scalars is None else f64(scalars, "scalars", VEC_SCALARS)
+    jobs, jobs2 = jobrows(jobs, "jobs"), jobrows(jobs2, "jobs2")
+    if partials is not None:
+        a.partials, a.partials_len = partials.ctypes.data, partials.size
+    a.scalars = scalars.ctypes.data
+    if cg is not None:
+        a.cg = cg.ctypes.data
+    if jobs is not None:
+        a.jobs, a.njobs = jobs.ctypes.data, jobs.shape[0]
+    if jobs2 is not None:
+        a.jobs2, a.njobs2 = jobs2.ctypes.data, jobs2.shape[0]
+    src = None
+    if overlay is not None:
+        src = np.ascontiguousarray(overlay[0], dtype=np.float64)
+        a.ov_slot[0], a.ov_slot[1] = (int(v) for v in overlay[1])
+        a.ov_n[0], a.ov_n[1] = (int(v) for v in overlay[2])
+        if src.size != a.ov_n[0] + a.ov_n[1]:
+            raise ValueError("overlay: src holds n[0] + n[1] doubles")
+        if src.size:
+            a.ov_src = src.ctypes.data
+    pub = np.full((4, VEC_SCALARS), np.nan)
+    info = np.zeros(4, dtype=np.int32)
+    a.pub, a.info = pub.ctypes.data, info.ctypes.data
+    if lib.PogsAmdVecCheck(ctypes.byref(a)) != 0:
+        raise RuntimeError(last_error())
+    return dict(x_out=xo, y_out=yo, partials=partials, scalars=scalars, cg=cg, pub=pub, info=[int(v) for v in info])
 
 
 def get_factor(handle, k, dtype):

@@ -14,6 +14,7 @@
 #include "spmv_check.h"
 #include "prox.h"
 #include "stream.h"
+#include "vec_check.h"
 #include "vec_kernels.h"
 
 namespace pogs_amd {
@@ -777,6 +778,13 @@ int PogsAmdGramCheck(int dtype, int kdim, int k, const void *P, size_t lda, int 
 int PogsAmdDensePassCheck(const PogsAmdDensePassArgs *args) {
   return guarded([&]() {
     dense_pass_check(args);
+    return 0;
+  });
+}
+
+int PogsAmdVecCheck(const PogsAmdVecArgs *args) {
+  return guarded([&]() {
+    vec_check(args);
     return 0;
   });
 }

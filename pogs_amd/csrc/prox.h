@@ -44,7 +44,9 @@ __device__ __forceinline__ float Cos(float a) { return cosf(a); }
 __device__ __forceinline__ double Cos(double a) { return cos(a); }
 
 // a * b rounded on its own: the empty asm makes the product opaque, so the compiler cannot contract
-// it with a following add / subtract into one fused multiply-add (-ffp-contract=fast is the default)
+// it with a following add / subtract into one fused multiply-add.  The build passes -ffp-contract=off to
+// every unit but gemm.hip (build.py), so this no longer rests on the compiler's default (-ffp-contract=fast
+// for HIP): it holds for any unit, and any flag set, that includes this header
 __device__ __forceinline__ float MulRn(float a, float b) {
   float p = a * b;
   asm volatile("" : "+v"(p));
