@@ -129,8 +129,18 @@ typedef struct PogsAmdOptions {
   int profile;         /* 1: bracket the dominant kernels with HIP events; k > 1:
                           every k-th such launch only (an event record costs the
                           stream a few microseconds of idle time)                   */
-  int reserved[5];
+  int reserved[5];     /* reserved[POGS_AMD_OPT_STORAGE] (= reserved[0]): the `storage` option, enum
+                          POGS_AMD_STORAGE, 0 = as dtype; reserved[1..4]: zero.  The array keeps
+                          its declaration so that an initialiser written for it --
+                          {dev, proj, prof, {0, 0, 0, 0, 0}} -- compiles and means what it meant
+                          (in strict C99 a struct has no second name for an array's element);
+                          zeroed options give the behaviour they always gave                 */
 } PogsAmdOptions;
+#define POGS_AMD_OPT_STORAGE 0
+#define PogsAmdOptStorage(opt) ((opt)->reserved[POGS_AMD_OPT_STORAGE])   /* lvalue: PogsAmdOptStorage(&o) = POGS_AMD_STORE_F32 */
+/* How a dense handle stores its matrix.  STORE_SAME: in the handle's dtype.  STORE_F32 (an fp64 handle): the
+ * equilibrated matrix is rounded to float and the one-pass iteration reads the float copy (PogsAmdCreateDense). */
+enum POGS_AMD_STORAGE { POGS_AMD_STORE_SAME = 0, POGS_AMD_STORE_F32 = 1 };
 
 typedef struct PogsAmdStats {
   /* last solve / iterate call */
@@ -187,7 +197,26 @@ int PogsAmdDistUniqueId(char *out);
  * tile is read twice per step), cg_iters the CG steps.  Every sum has one fixed order: two runs give the same bytes.
  * With dist->world > 1 both CGLS values are refused.  On a handle of either CGLS value PogsAmdSolveBatchFn,
  * PogsAmdSolveBatchWarmFn and PogsAmdGetFactor return POGS_ERROR and the handle stays usable.  PogsAmdCreateSparse
- * refuses CGLS_FUSED before anything is built. */
+ * refuses CGLS_FUSED before anything is built.
+ * PogsAmdOptStorage(opt) = POGS_AMD_STORE_F32 (mixed storage; the option lives in opt->reserved[0]): an fp64 handle
+ * over an fp32 copy of the matrix.  After the
+ * equilibration the stored matrix is rounded, entry by entry and to nearest, to values representable in float -- call
+ * it A^ -- and EVERYTHING in the handle is then defined on A^: the norm estimate, Gram matrix, factor, every product,
+ * the residuals and the epilogue.  The handle solves, in fp64 arithmetic throughout, the graph-form problem of the
+ * matrix D^-1 A^ E^-1, which differs from the caller's A by at most 2^-24 relative per entry; it is not an approximate
+ * projector on the unrounded matrix (d, e are those of the equilibration as it ran; PogsAmdGetEquil returns A^).  Two
+ * copies with equal values are kept: the fp64 one and a float one (rows of round_up(n, 4) floats, zero padding), so
+ * the matrix takes 1.5 x the memory of a plain fp64 handle's.  The hot launches of the one-pass iteration (lasso-like
+ * and logistic f: PogsAmdSolve, PogsAmdIterate) read the float copy, 4 bytes per entry instead of 8 (stats:
+ * stream_bytes counts such a launch as m n 4); every other pass -- set-up, the two-pass iteration, the pass after a
+ * missed rho prediction, the exact-residual pass of the lean form, PogsAmdMul, PogsAmdProject, the batch entries --
+ * reads the fp64 copy with its existing kernel.  Both copies hold the same numbers, so only the order of some sums
+ * differs.  POGS_AMD_MIXED_PASS=0 in the environment, read at create, keeps the rounding and both copies but runs
+ * every pass on the fp64 copy (the A / B leg of a measurement).
+ * Honoured for: dtype F64, m > n, projector DEFAULT or DIRECT, no dist, n <= 10240 (the row fits a one-pass shape of
+ * the mixed plan: not windowed and no wider than the fp64 one-pass iteration reaches).  Refused before anything is
+ * built -- POGS_ERROR, *out NULL, PogsAmdLastError names the reason: dtype F32, m <= n, either CGLS value, row shards,
+ * a wider or windowed row, an unknown storage value.  PogsAmdCreateSparse refuses any non-zero storage. */
 int PogsAmdCreateDense(PogsAmdSolver **out, int dtype, enum ORD ord, size_t m,
                        size_t n, const void *A, int mem,
                        const PogsAmdOptions *opt, const PogsAmdDist *dist);
@@ -694,6 +723,15 @@ typedef struct PogsAmdDensePassArgs {
   int *info;             /* 8 */
 } PogsAmdDensePassArgs;
 int PogsAmdDensePassCheck(const PogsAmdDensePassArgs *args);
+/* The same diagnostic for the mixed-storage pass (csrc/stream_mixed.h: an fp64 one-pass iteration's pass over a FLOAT
+ * matrix), by the launch functions a POGS_AMD_STORE_F32 handle calls.  Same struct, with these differences: dtype must
+ * be POGS_AMD_F64 (the type of every vector); M is float, rows x ldm, ldm a multiple of 4 and >= round_up(n, 4), its
+ * columns n .. round_up(n, 4) zero; forms ITER_FULL and ITER_LEAN, functors CHEAP and LOGISTIC, cols as above;
+ * force_tpb / force_nv name a one-pass shape of the MIXED plan (the 64- and 256-thread shapes of POGS_STREAM_PLANS,
+ * in float4 vectors: tpb nv 4 >= round_up(n, 4)), default make_stream_plan<float>(round_up(n, 4)); n <= 10240; dots
+ * must be NULL.  All vectors are doubles with the length contract above (col_len >= round_up(n, 2)); info as above
+ * (kernel = 3).  Invalid arguments are refused before any device work. */
+int PogsAmdDensePassMixedCheck(const PogsAmdDensePassArgs *args);
 /* Diagnostic of the kernels that do not read the matrix (csrc/vec_kernels.hip) and of the scalar block's way to the host
  * (csrc/engine.h: Ctx::queue_sum / fetch_scalars): ONE launch (plus the sum launch that follows it in a solve) on
  * caller-supplied HOST arrays, through the launch functions and block-count helpers the solvers call.  Every x-side array

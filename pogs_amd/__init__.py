@@ -10,6 +10,8 @@ from .graph import (  # noqa: F401
     FunctionVector,
     ManySolver,
     Ordering,
+    STORE_F32,
+    STORE_SAME,
     Solver,
     _solve_graph_form,
     dist_unique_id,
@@ -35,5 +37,5 @@ __version__ = "0.1.0"
 __all__ = [
     "solve_lasso", "solve_ridge", "solve_elastic_net", "solve_logistic", "solve_svm", "solve_huber",
     "solve_nonneg_ls", "solve_lasso_path", "solve_logistic_path", "solve_many", "pogs_solve", "Function", "FunctionObj", "FunctionVector", "Ordering", "Solver",
-    "ManySolver",
+    "ManySolver", "STORE_SAME", "STORE_F32",
 ]

@@ -54,6 +54,8 @@ HOST, DEVICE = 0, 1
 COL_MAJ, ROW_MAJ = 0, 1
 PROJ_DEFAULT, PROJ_DIRECT, PROJ_CGLS = 0, 1, 2
 PROJ_CGLS_FUSED = 3   # dense, one GPU: one pass over A per CG step, one host poll per iteration
+# enum POGS_AMD_STORAGE: how a dense handle stores its matrix (STORE_F32: an fp64 handle over a float copy)
+STORE_SAME, STORE_F32 = 0, 1
 
 
 class PogsAmdDist(ctypes.Structure):
@@ -61,7 +63,7 @@ class PogsAmdDist(ctypes.Structure):
 
 
 class PogsAmdOptions(ctypes.Structure):
-    _fields_ = [("device", c_int), ("projector", c_int), ("profile", c_int), ("reserved", c_int * 5)]
+    _fields_ = [("device", c_int), ("projector", c_int), ("profile", c_int), ("storage", c_int), ("reserved", c_int * 4)]
 
 
 class PogsAmdStats(ctypes.Structure):
@@ -252,7 +254,7 @@ ABI_SYMBOLS = [
     "PogsAmdReadBandwidth", "PogsAmdWaveSumCheck", "PogsAmdBlockIdCheck", "PogsAmdBatchRowsCheck", "PogsAmdBatchColsCheck",
     "PogsAmdSpBatchSpmvCheck", "PogsAmdManySetupCheck", "PogsAmdGramCheck", "PogsAmdCholCheck",
     "PogsAmdSpmvCheck", "PogsAmdSparseCgCheck", "PogsAmdGetFactor", "PogsAmdSparseGramCheck", "PogsAmdTriMatvecCheck",
-    "PogsAmdDensePassCheck", "PogsAmdDenseCgCheck", "PogsAmdVecCheck",
+    "PogsAmdDensePassCheck", "PogsAmdDenseCgCheck", "PogsAmdVecCheck", "PogsAmdDensePassMixedCheck",
 ]
 
 
@@ -580,8 +582,19 @@ PASS_COL_VECTORS = ("x0", "x1", "tot0", "tot1", "x_cur", "xt", "x12", "xtemp", "
 PASS_OUTPUTS = ("ytemp", "ynew", "y12s", "ytemps", "dots", "tot0", "tot1", "pack", "x12", "xtemp", "rhs")
 
 
+lib.PogsAmdDensePassMixedCheck.argtypes = [ctypes.POINTER(PogsAmdDensePassArgs)]
+PASS_KERNEL_MIXED = 3
+
+
+def dense_pass_mixed_check(form, M, n, vec, **kw):
+    """The mixed-storage pass (include/pogs_amd.h: PogsAmdDensePassMixedCheck): M float32, rows x ldm with ldm a multiple
+    of 4; every vector float64, column-side ones at least round_up(n, 2) long.  Arguments and result as
+    dense_pass_check; force names a one-pass shape of the mixed plan."""
+    return dense_pass_check(form, M, n, vec, _mixed=True, **kw)
+
+
 def dense_pass_check(form, M, n, vec, functor=PASS_FN_CHEAP, cols=PASS_COLS_REDUCE, f=None, g=None, rho=1.0, alpha=1.0,
-                     zs=1.0, c_old=0.0, num_cu=0, force=None):
+                     zs=1.0, c_old=0.0, num_cu=0, force=None, _mixed=False):
     """One dense streaming pass and its second stage by the solver's own kernels (include/pogs_amd.h:
     PogsAmdDensePassCheck).  M: rows x ldm; vec: dict of the vectors the form uses, by the names of the C struct
     (PASS_ROW_VECTORS of one length >= rows, PASS_COL_VECTORS of one length >= n_pad, "dots" of twice the row length,
@@ -601,7 +614,12 @@ def dense_pass_check(form, M, n, vec, functor=PASS_FN_CHEAP, cols=PASS_COLS_REDU
     for fn in (f, g):
         if fn is not None:
             typed += [np.ascontiguousarray(fn[k]) for k in "abcde"]
-    code = _dtype_code(M, *typed)
+    if _mixed:
+        if M.dtype != np.float32:
+            raise ValueError("M: float32")
+        code = _dtype_code(*typed) if typed else 1
+    else:
+        code = _dtype_code(M, *typed)
     if "pack" in arrs and arrs["pack"].dtype != np.float64:
         raise ValueError("pack: float64")
     vecw = 4 if code == 0 else 2
@@ -649,7 +667,7 @@ def dense_pass_check(form, M, n, vec, functor=PASS_FN_CHEAP, cols=PASS_COLS_REDU
     scalars, col_scalars = np.full(6, np.nan), np.full(4, np.nan)
     info = np.zeros(8, dtype=np.int32)
     a.scalars, a.col_scalars, a.info = scalars.ctypes.data, col_scalars.ctypes.data, info.ctypes.data
-    if lib.PogsAmdDensePassCheck(ctypes.byref(a)) != 0:
+    if (lib.PogsAmdDensePassMixedCheck if _mixed else lib.PogsAmdDensePassCheck)(ctypes.byref(a)) != 0:
         raise RuntimeError(last_error())
     out = {k: arrs[k] for k in PASS_OUTPUTS if k in arrs}
     out.update(scalars=scalars, col_scalars=col_scalars, info=dict(zip(PASS_INFO, (int(v) for v in info))))

@@ -9,6 +9,7 @@
 #include "factor_check.h"
 #include "many_kernels.h"
 #include "pass_check.h"
+#include "pass_check_mixed.h"
 #include "sparse_batch_kernels.h"
 #include "sparse_direct.h"
 #include "spmv_check.h"
@@ -87,6 +88,35 @@ inline void dense_pass_check(const PogsAmdDensePassArgs *a) {
 #undef POGS_PICK_PLAN
   throw Error("no dense pass check for this streaming shape");
 }
+// The storage option (PogsAmdOptStorage) of PogsAmdCreateDense: every combination POGS_AMD_STORE_F32 is not honoured
+// for is refused here, before anything is built (include/pogs_amd.h)
+inline void check_dense_storage(int dtype, size_t m, size_t n, const PogsAmdOptions *opt, const PogsAmdDist *dist) {
+  if (!opt || PogsAmdOptStorage(opt) == POGS_AMD_STORE_SAME) return;
+  POGS_CHECK(PogsAmdOptStorage(opt) == POGS_AMD_STORE_F32, "storage: unknown value (POGS_AMD_STORE_SAME or POGS_AMD_STORE_F32)");
+  POGS_CHECK(dtype == POGS_AMD_F64, "storage POGS_AMD_STORE_F32 needs dtype POGS_AMD_F64 (an fp32 handle already stores floats)");
+  POGS_CHECK(!(dist && dist->world >= 1), "storage POGS_AMD_STORE_F32 is single-GPU (row shards are not supported)");
+  POGS_CHECK(m > n, "storage POGS_AMD_STORE_F32 needs m > n");
+  POGS_CHECK(opt->projector == POGS_AMD_PROJ_DEFAULT || opt->projector == POGS_AMD_PROJ_DIRECT,
+             "storage POGS_AMD_STORE_F32 needs the direct projector (not CGLS or CGLS_FUSED)");
+  POGS_CHECK(n < (1u << 31) && make_mixed_plan(n, 256).ok,
+             "storage POGS_AMD_STORE_F32: the row is too wide (windowed, or past the 10240 columns the one-pass iteration reaches)");
+}
+
+// PogsAmdDensePassMixedCheck: refusals first (no device), then the launches (pass_check_mixed.h)
+inline void dense_pass_mixed_check(const PogsAmdDensePassArgs *a) {
+  POGS_CHECK(a != nullptr, "null argument: args");
+  pass_mixed_check_validate(*a);
+  int num_cu = a->num_cu;
+  if (num_cu == 0) {
+    int dev = 0;
+    hipDeviceProp_t prop;
+    POGS_HIP_CHECK(hipGetDevice(&dev));
+    POGS_HIP_CHECK(hipGetDeviceProperties(&prop, dev));
+    num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+  }
+  pass_mixed_check_run(*a, num_cu);
+}
+
 SolverBase *make_sparse_solver(int dtype, int ord, size_t m, size_t n, size_t nnz, const void *data,
                                const int *ptr, const int *ind, int mem, const PogsAmdOptions *opt,
                                const PogsAmdDist *dist);
@@ -329,6 +359,7 @@ int PogsAmdCreateDense(PogsAmdSolver **out, int dtype, enum ORD ord, size_t m, s
                        const PogsAmdOptions *opt, const PogsAmdDist *dist) {
   return guarded([&]() {
     *out = nullptr;
+    check_dense_storage(dtype, m, n, opt, dist);   // refused before anything is built
     DeviceGuard guard(opt ? opt->device : -1);   // the caller's current device is put back on exit
     std::unique_ptr<PogsAmdSolver> h(new PogsAmdSolver);
     h->impl.reset(make_dense_solver(dtype, ord, m, n, A, mem, opt, dist));
@@ -345,6 +376,7 @@ int PogsAmdCreateSparse(PogsAmdSolver **out, int dtype, enum ORD ord, size_t m, 
     // refused before anything is built: the sparse CGLS loop already is device-resident with one pass per product
     POGS_CHECK(!(opt && opt->projector == POGS_AMD_PROJ_CGLS_FUSED),
                "POGS_AMD_PROJ_CGLS_FUSED is a dense projector (a sparse handle: POGS_AMD_PROJ_CGLS runs the device-resident loop)");
+    POGS_CHECK(!(opt && PogsAmdOptStorage(opt) != POGS_AMD_STORE_SAME), "storage: a sparse handle stores its matrix in its dtype (POGS_AMD_STORE_SAME)");
     DeviceGuard guard(opt ? opt->device : -1);
     std::unique_ptr<PogsAmdSolver> h(new PogsAmdSolver);
     h->impl.reset(make_sparse_solver(dtype, ord, m, n, nnz, data, ptr, ind, mem, opt, dist));
@@ -778,6 +810,13 @@ int PogsAmdGramCheck(int dtype, int kdim, int k, const void *P, size_t lda, int 
 int PogsAmdDensePassCheck(const PogsAmdDensePassArgs *args) {
   return guarded([&]() {
     dense_pass_check(args);
+    return 0;
+  });
+}
+
+int PogsAmdDensePassMixedCheck(const PogsAmdDensePassArgs *args) {
+  return guarded([&]() {
+    dense_pass_mixed_check(args);
     return 0;
   });
 }

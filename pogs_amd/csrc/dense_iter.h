@@ -241,7 +241,7 @@ bool DenseSolver<T, Tag>::iteration_fused(unsigned verbose) {
 #define POGS_LEAN_F32_NV5 0
 #endif
   constexpr bool kLeanType = std::is_same<T, double>::value || (POGS_LEAN_F32_NV5 != 0 && Tag::has(256, 5) && !Tag::windows);
-  const bool lean = kLeanType && !multi_ && !exact_mode_;
+  const bool lean = kLeanType && !multi_ && !exact_mode_ && !mixed_full_;
   int nparts = colparts_ > 0 ? colparts_ : stream2_grid<2>(planA_, m_);
   if (!spec) {
     // (A') y half of the prox / over-relaxation, then (B) the column sums A^T yhat_k and
@@ -305,9 +305,30 @@ bool DenseSolver<T, Tag>::iteration_fused(unsigned verbose) {
     // speculate on the rho the adaptive rule is expected to choose (the previous
     // iteration's residuals stand in for this one's)
     ctl_.predict(&rho_pred_, &zs_pred_);
-    ctx_.stream_timer.begin(s);
+    const bool timed = ctx_.stream_timer.begin(s) != EventTimer::npos;
     int grid = stream2_grid<2>(planA_, m_);
-    if (fused_logistic_) {
+    bool mixed_done = false;
+    if constexpr (std::is_same<T, double>::value) {
+      // mixed storage: the same four launches over the float copy (stream_mixed.h: same functor, same partial-sum
+      // layout, the mixed plan's grid); A32_ holds the values of A_, so only the order of the sums differs
+      if (mixed_pass_) {
+        const StreamArgsMixed am{A32_.p, lda32_, m_, n_pad_, static_cast<int>(lda32_), x_[nw].p, x12_.p, colpart_.p, colpart2_.p,
+                                 ctx_.spart.p};
+        if (fused_logistic_) {
+          launch_stream2_mixed(planM_, !lean, am, FusedIterOp<double, true>{y_[nw].p, y_[cur_].p, y12_.p, ytemp_.p, fview(), rho_pred_,
+                                                                            ctl_.alpha(), zs_pred_, y12s_.p, ytemps_.p}, s);
+        } else {
+          launch_stream2_mixed(planM_, !lean, am, FusedIterOp<double, false>{y_[nw].p, y_[cur_].p, y12_.p, ytemp_.p, fview(), rho_pred_,
+                                                                             ctl_.alpha(), zs_pred_, y12s_.p, ytemps_.p}, s);
+        }
+        grid = mixed_grid(planM_, !lean, m_);
+        if (timed) ++mixed_timed_;
+        mixed_done = true;
+      }
+    }
+    if (mixed_done) {
+      // (the launch above)
+    } else if (fused_logistic_) {
       FusedIterOp<T, true> op{y_[nw].p, y_[cur_].p, y12_.p, ytemp_.p, fview(), rho_pred_, ctl_.alpha(), zs_pred_,
                               y12s_.p, ytemps_.p};
       if constexpr (kLeanType) {
@@ -464,5 +485,8 @@ void DenseSolver<T, Tag>::collect_stream_timer() {
   unsigned long long cnt = 0;
   ctx_.stats.stream_ms += ctx_.stream_timer.collect_ms(&cnt);
   ctx_.stats.stream_launches += cnt;
-  ctx_.stats.stream_bytes += static_cast<double>(cnt) * m_ * n_ * sizeof(T);
+  // (a mixed launch reads the float copy: m n 4 bytes)
+  const unsigned long long mixed = std::min(mixed_timed_, cnt);
+  mixed_timed_ = 0;
+  ctx_.stats.stream_bytes += static_cast<double>(cnt - mixed) * m_ * n_ * sizeof(T) + static_cast<double>(mixed) * m_ * n_ * sizeof(float);
 }

@@ -80,7 +80,10 @@ void DenseSolver<T, Tag>::alloc_state() {
   if (tmode_) { uvec_.alloc(mp); uvec_.zero(s); }
   xout_.alloc(np); yout_.alloc(m_); lout_.alloc(m_); muout_.alloc(np);
   f_.alloc(m_); g_.alloc(n_); fs_.alloc(m_); gs_.alloc(n_);
-  colpart_.alloc(static_cast<size_t>(planA_.grid_max) * scols_pad_);
+  // (mixed storage: the mixed plan's launches may use more workgroups than planA_'s -- the partial-sum buffers take
+  //  the larger of the two)
+  const size_t gmax = std::max<size_t>(planA_.grid_max, mixed_store_ ? mixed_grid_max(planM_) : 0);
+  colpart_.alloc(gmax * scols_pad_);
   ensure_xl(planA_, srows_, scols_pad_);
   if (use_cgls_) {
     cg_p_.alloc(np); cg_s_.alloc(np); cg_q_.alloc(m_); cg_r_.alloc(m_); cg_.alloc(kCgNumSlots);
@@ -94,7 +97,7 @@ void DenseSolver<T, Tag>::alloc_state() {
     x12s_.alloc(np); xtemps_.alloc(np);
     x12s_.zero(s); xtemps_.zero(s);
   } else if (fused_ok_) {
-    colpart2_.alloc(static_cast<size_t>(planA_.grid_max) * np);
+    colpart2_.alloc(gmax * np);
     if (multi_) {   // [A^T yhat | exact-dual-residual sums | 6 scalars] in fp64: one all-reduce per iteration
       pack_.alloc(2 * np + 8);
       pack_.zero(s);
@@ -106,10 +109,18 @@ void DenseSolver<T, Tag>::alloc_state() {
   // of the one-pass iteration | its projection-tail partials] -- the last two have regions of
   // their own because that iteration sums everything in its closing launch (Ctx::queue_sum)
   const size_t vb = vec_blocks(n_) + vec_blocks(m_);
-  const size_t r01 = static_cast<size_t>(planA_.grid_max) * 6 + std::max<size_t>(4096, vb * 3 + 64);
+  const size_t r01 = gmax * 6 + std::max<size_t>(4096, vb * 3 + 64);
   sp_pre_off_ = r01;   // [y-half prox sums: vec_blocks(m) x 3 | pre_cols sums: column blocks x 4]
   sp_tail_off_ = r01 + vb * 3 + static_cast<size_t>(pre_cols_grid(n_pad_, Vec16<T>::N)) * 4 + 64;
   ctx_.ensure_spart(sp_tail_off_ + static_cast<size_t>(ctx_.num_cu) * 32);
+  if (mixed_store_) {
+    A32_.alloc(static_cast<size_t>(m_) * lda32_);
+    // POGS_AMD_MIXED_PASS=0: the matrix is still rounded and both copies built, but step (D) stays on A_ (A / B leg)
+    const char *mp = std::getenv("POGS_AMD_MIXED_PASS");
+    mixed_pass_ = fused_ok_ && !(mp && mp[0] == '0');
+    const char *mf = std::getenv("POGS_AMD_MIXED_FULL");
+    mixed_full_ = mixed_pass_ && mf && mf[0] == '1';
+  }
 }
 
 // MatrixDense::Equil without materialising A.^2 (matrix_dense.cpp:116-200,
@@ -248,6 +259,15 @@ void DenseSolver<T, Tag>::equilibrate() {
   const T invs = static_cast<T>(1) / std::sqrt(normA);                   // :191-192
   launch_scal<T>(d_.p, invs, m_, s);
   launch_scal<T>(e_.p, invs, n_, s);
+  // Mixed storage: the stored matrix is rounded to float, entry by entry, and A_ made equal to the float copy, so
+  // that everything from here on -- norm estimate, Gram matrix, factor, every pass -- is defined on the rounded matrix
+  // (the factor and the passes see the same numbers).  d, e and the row sums are those of the equilibration as it ran.
+  if constexpr (std::is_same<T, double>::value) {
+    if (mixed_store_) {
+      launch_round_to_f32(A_.p, lda_, A32_.p, lda32_, m_, n_, sgrid, s);
+      amax_ *= 1.0 + 1.0 / (1 << 23);   // (rounding may move the largest |entry| up by half a float ulp)
+    }
+  }
   ctx_.stats.equil_ms = pt.stop_ms();
 }
 

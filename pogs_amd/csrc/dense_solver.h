@@ -33,6 +33,7 @@
 #include "ops.h"
 #include "reduce.h"
 #include "stream.h"
+#include "stream_mixed.h"
 #include "vec_kernels.h"
 
 namespace pogs_amd {
@@ -144,6 +145,14 @@ class DenseSolver final : public SolverBase {
     cg_fused_ = opt && opt->projector == POGS_AMD_PROJ_CGLS_FUSED;
     use_cgls_ = cg_fused_ || (opt && opt->projector == POGS_AMD_PROJ_CGLS);
     if (const char *ys = std::getenv("POGS_AMD_YSYNC")) ysync_ = std::max(0, std::atoi(ys));
+    // mixed storage (stream_mixed.h; the combinations it is honoured for are checked in abi.hip before anything is built)
+    mixed_store_ = std::is_same<T, double>::value && opt && PogsAmdOptStorage(opt) == POGS_AMD_STORE_F32;
+    if (mixed_store_) {
+      POGS_CHECK(tall_ && !multi_ && !use_cgls_, "POGS_AMD_STORE_F32 needs m > n, the direct projector and one GPU");
+      planM_ = make_mixed_plan(n, ctx_.num_cu);
+      POGS_CHECK(planM_.ok, "POGS_AMD_STORE_F32: the row fits no one-pass shape of the mixed plan");
+      lda32_ = round_up(n, 4);
+    }
     POGS_CHECK(!(use_cgls_ && multi_), "the CGLS projector is single-GPU");
     constexpr int VEC = Vec16<T>::N;
     n_pad_ = static_cast<int>(round_up(n, VEC));
@@ -591,6 +600,14 @@ class DenseSolver final : public SolverBase {
   std::vector<size_t> cgf_events_;   // fused loop: the timer brackets of the enqueued passes
   size_t lda_ = 0;
   StreamPlan planA_, planW_;
+  // mixed storage (POGS_AMD_STORE_F32, stream_mixed.h): A_ holds the rounded matrix, A32_ the same values as floats
+  // (m x lda32_, lda32_ = round_up(n, 4), zero padding); step (D) of iteration_fused reads A32_ when mixed_pass_
+  bool mixed_store_ = false, mixed_pass_ = false;
+  bool mixed_full_ = false;     // POGS_AMD_MIXED_FULL=1 (measurement aid): the full form from the first iteration
+  MixedPlan planM_;
+  DevBuf<float> A32_;
+  size_t lda32_ = 0;
+  unsigned long long mixed_timed_ = 0;   // bracketed mixed launches since the last collect_stream_timer
   const T *A_src_ = nullptr;    // upload() .. equilibrate(): the caller's device buffer standing in for A_
   bool pre_cheap_ = false;      // every f_i, g_j has a few-operation prox (admm_pre_kernel inlines it)
   T *Wp_ = nullptr, *Up_ = nullptr;   // views into fac_

@@ -177,6 +177,33 @@ def _resolve_dtype(dtype):
     return dt
 
 
+STORE_SAME, STORE_F32 = _lib.STORE_SAME, _lib.STORE_F32
+
+
+def _resolve_storage(storage, dtype):
+    """Solver(storage=...) as STORE_SAME / STORE_F32: None, np.float64, np.float32 or one of the two constants."""
+    if storage is None:
+        return STORE_SAME
+    if isinstance(storage, (int, np.integer)) and not isinstance(storage, bool):
+        if int(storage) not in (STORE_SAME, STORE_F32):
+            raise ValueError("storage must be None, np.float64, np.float32, STORE_SAME or STORE_F32")
+        code = int(storage)
+    else:
+        try:
+            sdt = np.dtype(storage)
+        except TypeError:
+            raise ValueError("storage must be None, np.float64, np.float32, STORE_SAME or STORE_F32") from None
+        if sdt == np.dtype(np.float32):
+            code = STORE_F32
+        elif sdt == np.dtype(np.float64) and dtype == np.dtype(np.float64):
+            code = STORE_SAME
+        else:
+            raise ValueError("storage must be None, np.float64, np.float32, STORE_SAME or STORE_F32")
+    if code == STORE_F32 and dtype != np.dtype(np.float64):
+        raise ValueError("storage=float32 needs dtype=float64 (a float32 solver already stores float32)")
+    return code
+
+
 def _ptr(a):
     return a.ctypes.data_as(ctypes.c_void_p)
 
@@ -534,14 +561,20 @@ class Solver:
     min(m, n) <= SPARSE_DIRECT_MAX on one GPU the exact projector: two products and two triangular mat-vecs per
     iteration instead of a CGLS loop (the one-shot ``solve_*`` calls keep CGLS).  PROJ_CGLS_FUSED (dense, one GPU):
     CGLS with one pass over A per CG step and one host poll per iteration (include/pogs_amd.h: PogsAmdCreateDense).
+    ``storage``: None / np.float64 on a float64 solver / STORE_SAME: the matrix is stored in ``dtype``.  np.float32 or
+    STORE_F32 with ``dtype=np.float64`` (dense, m > n, direct projector, one GPU, n <= 10240): mixed storage -- the
+    equilibrated matrix is rounded to float32 and the handle solves, in float64 arithmetic, the problem of that rounded
+    matrix; ``solve`` and ``iterate`` read the float32 copy (1.5 x the matrix memory; PogsAmdCreateDense).  The
+    attribute ``storage`` holds STORE_SAME or STORE_F32.
     """
 
     def __init__(self, A, dtype=None, shape=None, device_ptr=False, order=Ordering.ROW_MAJ, device=-1,
-                 profile=False, projector=_lib.PROJ_DEFAULT, dist=None):
+                 profile=False, projector=_lib.PROJ_DEFAULT, dist=None, storage=None):
         self.dtype = _resolve_dtype(dtype)
+        self.storage = _resolve_storage(storage, self.dtype)   # (ValueError before the library is called)
         self._h = ctypes.c_void_p()
         code = _lib.F64 if self.dtype == np.float64 else _lib.F32
-        opt = _lib.PogsAmdOptions(device=device, projector=projector, profile=int(profile))
+        opt = _lib.PogsAmdOptions(device=device, projector=projector, profile=int(profile), storage=self.storage)
         dist_s = None
         self._m_global = None   # row shards: the rows of the whole matrix
         if dist is not None:
