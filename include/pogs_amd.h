@@ -402,6 +402,35 @@ int PogsAmdManySolveFn(PogsAmdMany *h, const PogsAmdFn *f, const PogsAmdFn *g, c
 int PogsAmdManyGetInfo(const PogsAmdMany *h, PogsAmdManyInfo *out);
 void PogsAmdManyDestroy(PogsAmdMany *h);
 
+/* Ragged many-problem solves: the k problems of PogsAmdSolveManyFn, problem j with its own shape m[j] x n[j].  The
+ * same kernels solve them, one workgroup per problem, and problem j's outputs are the bytes PogsAmdSolveManyFn
+ * returns for it alone (k = 1), whatever its position, its neighbours and the chunks.
+ * PogsAmdSolveManyRaggedFn: m, n: HOST arrays of k shapes.  Every packed array holds the problems back to back:
+ *    A: matrix j at element offset sum_{i<j} m[i] n[i], each in `ord`, host or device (mem); the offset may have any
+ *       element alignment; a device A is never written.
+ *    f[j] describes m[j] entries and g[j] n[j] entries: a caller that packs its coefficient arrays puts problem j's
+ *       at row offset sum_{i<j} m[i] (f) / column offset sum_{i<j} n[i] (g) and points f[j], g[j] there.
+ *    Outputs (HOST): x, mu at the column offset; y, l at the row offset; optval, final_iter, status at j.
+ *    Every other argument as in PogsAmdSolveManyFn.  Envelope, per problem: 1 <= min(m[j], n[j]) <=
+ *    POGS_AMD_MANY_MIN_DIM_MAX and max(m[j], n[j]) <= POGS_AMD_MANY_MAX_DIM_MAX.  Chunks are packed by each
+ *    problem's own footprint under POGS_AMD_MANY_WORKSPACE_MB; a chunk holds at least one problem.
+ *    Refused with POGS_ERROR before any device work, no output written, PogsAmdLastError naming the argument and, for
+ *    a shape, the problem's index: k < 1; NULL m, n, A, f, g, x, final_iter or status; an unknown ord, dtype or mem;
+ *    a problem outside the envelope; CGLS.
+ * PogsAmdManyCreateRagged: PogsAmdManyCreate over ragged problems (arguments and refusals as above).  The handle is
+ *    a PogsAmdMany: PogsAmdManySolveFn (all three starts, rho_final), PogsAmdManyGetInfo and PogsAmdManyDestroy work
+ *    on it with the ragged layouts above (x0 at the column offsets, l0 at the row offsets).  PogsAmdManyInfo.m / .n
+ *    report the largest m[j] / n[j].
+ * PogsAmdManyGetShapes: the k shapes of a handle of either kind into m and n (k values each). */
+int PogsAmdSolveManyRaggedFn(int dtype, enum ORD ord, int k, const size_t *m, const size_t *n, const void *A, int mem,
+                             const PogsAmdOptions *opt, const PogsAmdFn *f, const PogsAmdFn *g, const double *rho,
+                             double abs_tol, double rel_tol, unsigned int max_iter, unsigned int verbose,
+                             int adaptive_rho, int gap_stop, void *x, void *y, void *l, void *mu,
+                             double *optval, unsigned int *final_iter, int *status);
+int PogsAmdManyCreateRagged(PogsAmdMany **out, int dtype, enum ORD ord, int k, const size_t *m, const size_t *n,
+                            const void *A, int mem, const PogsAmdOptions *opt);
+int PogsAmdManyGetShapes(const PogsAmdMany *h, size_t *m, size_t *n);
+
 /* Benchmark stepping.  PogsAmdBeginRun loads f/g and the solve parameters and
  * resets the ADMM state to the cold start; PogsAmdIterate then advances exactly
  * `iters` ADMM iterations of real solves (restarting from the cold start each

@@ -24,6 +24,7 @@ from .graph import (  # noqa: F401
     solve_lasso,
     solve_lasso_path,
     solve_many,
+    solve_many_ragged,
     solve_logistic,
     solve_logistic_path,
     solve_nonneg_ls,
@@ -36,6 +37,6 @@ from .cvxpy import pogs_solve  # noqa: E402,F401  (reference: python/pogs/__init
 __version__ = "0.1.0"
 __all__ = [
     "solve_lasso", "solve_ridge", "solve_elastic_net", "solve_logistic", "solve_svm", "solve_huber",
-    "solve_nonneg_ls", "solve_lasso_path", "solve_logistic_path", "solve_many", "pogs_solve", "Function", "FunctionObj", "FunctionVector", "Ordering", "Solver",
+    "solve_nonneg_ls", "solve_lasso_path", "solve_logistic_path", "solve_many", "solve_many_ragged", "pogs_solve", "Function", "FunctionObj", "FunctionVector", "Ordering", "Solver",
     "ManySolver", "STORE_SAME", "STORE_F32",
 ]

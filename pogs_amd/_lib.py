@@ -158,6 +158,16 @@ lib.PogsAmdManySolveFn.argtypes = [c_void_p, ctypes.POINTER(PogsAmdFn), ctypes.P
                                    c_void_p, c_void_p, c_double, c_double, c_uint, c_uint, c_int, c_int, c_void_p,
                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
 lib.PogsAmdManyGetInfo.argtypes = [c_void_p, ctypes.POINTER(PogsAmdManyInfo)]
+lib.PogsAmdSolveManyRaggedFn.argtypes = [c_int, c_int, c_int, ctypes.POINTER(c_size_t), ctypes.POINTER(c_size_t), c_void_p,
+                                         c_int, ctypes.POINTER(PogsAmdOptions), ctypes.POINTER(PogsAmdFn),
+                                         ctypes.POINTER(PogsAmdFn), c_void_p, c_double, c_double, c_uint, c_uint, c_int,
+                                         c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+lib.PogsAmdSolveManyRaggedFn.restype = c_int
+lib.PogsAmdManyCreateRagged.argtypes = [ctypes.POINTER(c_void_p), c_int, c_int, c_int, ctypes.POINTER(c_size_t),
+                                        ctypes.POINTER(c_size_t), c_void_p, c_int, ctypes.POINTER(PogsAmdOptions)]
+lib.PogsAmdManyCreateRagged.restype = c_int
+lib.PogsAmdManyGetShapes.argtypes = [c_void_p, ctypes.POINTER(c_size_t), ctypes.POINTER(c_size_t)]
+lib.PogsAmdManyGetShapes.restype = c_int
 lib.PogsAmdManyDestroy.argtypes = [c_void_p]
 lib.PogsAmdManyDestroy.restype = None
 lib.PogsAmdBeginRunFn.argtypes = [c_void_p, ctypes.POINTER(PogsAmdFn), ctypes.POINTER(PogsAmdFn), c_double, c_double, c_double,
@@ -247,6 +257,7 @@ ABI_SYMBOLS = [
     "PogsAmdDistUniqueId", "PogsAmdCreateDense", "PogsAmdCreateSparse", "PogsAmdSolve", "PogsAmdSolveFn", "PogsAmdSolveBatchFn", "PogsAmdSolveBatchSparseFn",
     "PogsAmdSolveBatchWarmFn",
     "PogsAmdSolveManyFn", "PogsAmdManyCreate", "PogsAmdManySolveFn", "PogsAmdManyGetInfo", "PogsAmdManyDestroy",
+    "PogsAmdSolveManyRaggedFn", "PogsAmdManyCreateRagged", "PogsAmdManyGetShapes",
     "PogsAmdBeginRun", "PogsAmdBeginRunFn",
     "PogsAmdIterate", "PogsAmdSetWarmStart", "PogsAmdGetStats", "PogsAmdResetStats", "PogsAmdDestroy", "PogsAmdLastError",
     "PogsAmdPoolStats", "PogsAmdPoolTrim",

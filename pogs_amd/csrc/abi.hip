@@ -525,6 +525,51 @@ int PogsAmdManyCreate(PogsAmdMany **out, int dtype, enum ORD ord, int k, size_t 
   });
 }
 
+int PogsAmdSolveManyRaggedFn(int dtype, enum ORD ord, int k, const size_t *m, const size_t *n, const void *A, int mem,
+                             const PogsAmdOptions *opt, const PogsAmdFn *f, const PogsAmdFn *g, const double *rho,
+                             double abs_tol, double rel_tol, unsigned int max_iter, unsigned int verbose,
+                             int adaptive_rho, int gap_stop, void *x, void *y, void *l, void *mu, double *optval,
+                             unsigned int *final_iter, int *status) {
+  return guarded([&]() {
+    POGS_CHECK(k >= 1, "ragged many-problem solve: k must be >= 1");
+    const int projector = opt ? opt->projector : POGS_AMD_PROJ_DEFAULT;
+    POGS_CHECK(projector == POGS_AMD_PROJ_DEFAULT || projector == POGS_AMD_PROJ_DIRECT,
+               "ragged many-problem solve: only the direct projector is supported (CGLS refused)");
+    const int device = opt ? opt->device : -1;
+    many_check_ragged(dtype, static_cast<int>(ord), k, m, n, A, mem);
+    const auto fg = fn_hosts("ragged many-problem solve", k, f, g, x, final_iter, status);
+    DeviceGuard guard(device);
+    solve_many_ragged(dtype, static_cast<int>(ord), k, m, n, A, mem, device, fg.first.data(), fg.second.data(), rho,
+                      make_params(1.0, abs_tol, rel_tol, max_iter, verbose, adaptive_rho, gap_stop),
+                      BatchOut{x, y, l, mu, optval, final_iter, status});
+    return 0;
+  });
+}
+
+int PogsAmdManyCreateRagged(PogsAmdMany **out, int dtype, enum ORD ord, int k, const size_t *m, const size_t *n,
+                            const void *A, int mem, const PogsAmdOptions *opt) {
+  return guarded([&]() {
+    POGS_CHECK(out != nullptr, "many-problem handle: null out");
+    *out = nullptr;
+    POGS_CHECK(k >= 1, "ragged many-problem solve: k must be >= 1");
+    const int projector = opt ? opt->projector : POGS_AMD_PROJ_DEFAULT;
+    POGS_CHECK(projector == POGS_AMD_PROJ_DEFAULT || projector == POGS_AMD_PROJ_DIRECT,
+               "ragged many-problem solve: only the direct projector is supported (CGLS refused)");
+    std::unique_ptr<PogsAmdMany> h(new PogsAmdMany);
+    h->impl.reset(many_create_ragged(dtype, static_cast<int>(ord), k, m, n, A, mem, opt ? opt->device : -1));
+    *out = h.release();
+    return 0;
+  });
+}
+
+int PogsAmdManyGetShapes(const PogsAmdMany *h, size_t *m, size_t *n) {
+  return guarded([&]() {
+    POGS_CHECK(h && h->impl && m && n, "null argument");
+    h->impl->shapes(m, n);
+    return 0;
+  });
+}
+
 int PogsAmdManySolveFn(PogsAmdMany *h, const PogsAmdFn *f, const PogsAmdFn *g, const double *rho, int start,
                        const void *x0, const void *l0, double abs_tol, double rel_tol, unsigned int max_iter,
                        unsigned int verbose, int adaptive_rho, int gap_stop, void *x, void *y, void *l, void *mu,

@@ -38,9 +38,20 @@ struct ManyHandle {
   virtual void solve(const FnHost *f, const FnHost *g, const ManyStart &st, const SolveParams &p,
                      const BatchOut &out) = 0;
   virtual PogsAmdManyInfo info() const = 0;
+  // the count() shapes (PogsAmdManyGetShapes); a uniform handle repeats its one shape
+  virtual void shapes(size_t *m, size_t *n) const = 0;
 };
 
 // Checks as solve_many's (many_check_args), before any device work; then upload, setup, and the resident buffers.
 ManyHandle *many_create(int dtype, int ord, int k, size_t m, size_t n, const void *A, int mem, int device);
+
+// The ragged forms (PogsAmdSolveManyRaggedFn, PogsAmdManyCreateRagged): problem j is m[j] x n[j], its matrix at
+// element offset sum_{i<j} m[i] n[i] of A, its rows / columns at sum_{i<j} m[i] / n[i] of every packed array.  The
+// same driver, kernels and handle class; refusals name the argument and, for a shape, the problem.
+void many_check_ragged(int dtype, int ord, int k, const size_t *m, const size_t *n, const void *A, int mem);
+void solve_many_ragged(int dtype, int ord, int k, const size_t *m, const size_t *n, const void *A, int mem, int device,
+                       const FnHost *f, const FnHost *g, const double *rho, const SolveParams &p, const BatchOut &out);
+ManyHandle *many_create_ragged(int dtype, int ord, int k, const size_t *m, const size_t *n, const void *A, int mem,
+                               int device);
 
 }  // namespace pogs_amd

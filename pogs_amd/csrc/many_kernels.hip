@@ -11,6 +11,11 @@
 // fixed butterflies, partials combined in index order), and a problem's arithmetic never looks at its index, the
 // chunk or the other problems: its bytes are its own.
 //
+// The ragged entries (PogsAmdSolveManyRaggedFn / PogsAmdManyCreateRagged) give every problem its own shape: a table
+// with one row per problem (ManyProb) tells each workgroup its (m, n) and where its data lives, and many_problem(),
+// called once at the top of every kernel, turns the kernel's arguments into that problem's; the code below it is the
+// same for both layouts.
+//
 // The persistent handle (PogsAmdManyCreate / PogsAmdManySolveFn) runs the same setup once, keeps all k problems
 // resident and opens every solve with many_begin_kernel: cold, or warm from a problem's kept x, l and rho.
 #include <algorithm>
@@ -61,13 +66,23 @@ struct ManyState {
 enum XVec : int { kX = 0, kXt, kXprev, kX12, kXtemp, kE, kXs, kNumX };
 enum YVec : int { kY = 0, kYt, kYprev, kY12, kYtemp, kD, kYs, kNumY };
 
+// One row of the ragged table (ManyArgs::prob): problem q's own shape, where it lives in every pool (element
+// offsets from the pools' base pointers in ManyArgs), its Sinkhorn-Knopp regularisers and its iteration bound.
+template <typename T>
+struct ManyProb {
+  int m, n;
+  int ipl, pad;                  // ADMM iterations per loop launch (many_iters_per_launch of its shape)
+  size_t ws, src, xo, yo;        // workspace; staged input; x-sized outputs (x, mu); y-sized outputs (y, l)
+  T ce, cd;
+};
+
 template <typename T>
 struct ManyArgs {
   int m, n, k, tall;
   size_t stride;                 // elements of T per problem in ws
   size_t oA, oW, oT, ox[kNumX], oy[kNumY];
   T *ws;
-  const T *src;                  // the chunk's input matrices, problem q at q*m*n
+  const T *src;                  // the chunk's input matrices, problem q at q*m*n (ragged: at prob[q].src)
   int rowmaj;
   const T *rnd;                  // Norm2Est start vector (n)
   const ManyFn<T> *fn;           // f of problem q at 2q, g at 2q + 1
@@ -75,11 +90,54 @@ struct ManyArgs {
   ManyState<T> *st;
   unsigned *done_count;
   T ce, cd;                      // Sinkhorn-Knopp regularisers (equil_helper.h:152-160)
-  T *xo, *yo, *lo, *muo;         // chunk outputs, problem q at q*n / q*m
+  T *xo, *yo, *lo, *muo;         // chunk outputs, problem q at q*n / q*m (ragged: at prob[q].xo / .yo)
   double *optval;
   unsigned *iters;
   int *status;
+  const ManyProb<T> *prob;       // ragged: one row per problem; nullptr: every problem m x n, problem q at q * stride
+  size_t src0;                   // ragged: the element offset (as the rows' src counts) of the matrix src points at
 };
+
+// A problem's workspace layout from its shape alone (offsets in elements of T): every array starts on a multiple of
+// 64 elements, and so does the next problem's workspace.
+template <typename T>
+__host__ __device__ __forceinline__ void many_offsets(ManyArgs<T> &a, int m, int n) {
+  const int K = m < n ? m : n;
+  const size_t mz = static_cast<size_t>(m), nz = static_cast<size_t>(n), Kz = static_cast<size_t>(K);
+  const size_t rm = (mz + 63) / 64 * 64, rn = (nz + 63) / 64 * 64;
+  a.m = m; a.n = n; a.k = K; a.tall = m > n;
+  size_t off = 0;
+  a.oA = off; off += (mz * nz + 63) / 64 * 64;
+  a.oW = off; off += (Kz * Kz + 63) / 64 * 64;
+  a.oT = off; off += (Kz + 63) / 64 * 64;
+  for (int v = 0; v < kNumX; ++v) { a.ox[v] = off; off += rn; }
+  for (int v = 0; v < kNumY; ++v) { a.oy[v] = off; off += rm; }
+  a.stride = off;
+}
+
+// Problem q's view of the arguments, taken once at the top of every kernel: afterwards a.m, a.n, a.k, a.tall and the
+// offsets are the problem's own, and ws, src, xo, yo, lo, muo point at the problem's own data (the per-problem arrays
+// fn, ctl, st, optval, iters and status stay indexed by q).  Uniform (prob == nullptr): the shape is the kernel-wide
+// one and the pointers advance by q problems.  Returns the problem's bound on the iterations of one loop launch.
+// Everything here is uniform over the workgroup.
+template <typename T>
+__device__ __forceinline__ int many_problem(ManyArgs<T> &a, int q) {
+  if (!a.prob) {
+    a.ws += q * a.stride;
+    a.src += q * (static_cast<size_t>(a.m) * a.n);
+    a.xo += static_cast<size_t>(q) * a.n; a.muo += static_cast<size_t>(q) * a.n;
+    a.yo += static_cast<size_t>(q) * a.m; a.lo += static_cast<size_t>(q) * a.m;
+    return kMaxIterPerLaunch;
+  }
+  const ManyProb<T> p = a.prob[q];
+  many_offsets(a, p.m, p.n);
+  a.ce = p.ce; a.cd = p.cd;
+  a.ws += p.ws;
+  a.src += p.src - a.src0;
+  a.xo += p.xo; a.muo += p.xo;
+  a.yo += p.yo; a.lo += p.yo;
+  return p.ipl;
+}
 
 // ---- workgroup building blocks -------------------------------------------------------------------
 
@@ -173,9 +231,10 @@ __device__ __forceinline__ Coef<T> coef(const ManyFn<T> &F, int i, T s, bool isf
 template <typename T>
 __global__ __launch_bounds__(kTPB) void many_copy_kernel(ManyArgs<T> a) {
   const int q = blockIdx.y;
+  many_problem(a, q);
   const size_t mn = static_cast<size_t>(a.m) * a.n;
-  const T *src = a.src + q * mn;
-  T *A = a.ws + q * a.stride + a.oA;
+  const T *src = a.src;
+  T *A = a.ws + a.oA;
   for (size_t idx = static_cast<size_t>(blockIdx.x) * kTPB + threadIdx.x; idx < mn;
        idx += static_cast<size_t>(gridDim.x) * kTPB) {
     const size_t i = idx / a.n, c = idx % a.n;
@@ -187,8 +246,10 @@ __global__ __launch_bounds__(kTPB) void many_copy_kernel(ManyArgs<T> a) {
 template <typename T>
 __global__ __launch_bounds__(kTPB) void many_sk_kernel(ManyArgs<T> a, int p0, int np) {
   __shared__ T part[kTPB];
-  const int q = blockIdx.x, m = a.m, n = a.n;
-  T *w = a.ws + q * a.stride;
+  const int q = blockIdx.x;
+  many_problem(a, q);
+  const int m = a.m, n = a.n;
+  T *w = a.ws;
   const T *A = w + a.oA;
   T *d = w + a.oy[kD], *e = w + a.ox[kE];
   if (p0 == 0) {
@@ -209,8 +270,10 @@ __global__ __launch_bounds__(kTPB) void many_sk_kernel(ManyArgs<T> a, int p0, in
 template <typename T>
 __global__ __launch_bounds__(kTPB) void many_scale_kernel(ManyArgs<T> a) {
   __shared__ double red[1 * (kWaves + 1)];
-  const int q = blockIdx.x, m = a.m, n = a.n;
-  T *w = a.ws + q * a.stride;
+  const int q = blockIdx.x;
+  many_problem(a, q);
+  const int m = a.m, n = a.n;
+  T *w = a.ws;
   T *A = w + a.oA, *d = w + a.oy[kD], *e = w + a.ox[kE];
   for (int i = threadIdx.x; i < m; i += kTPB) d[i] = dev::Sqrt(d[i]);
   for (int j = threadIdx.x; j < n; j += kTPB) e[j] = dev::Sqrt(e[j]);
@@ -240,10 +303,12 @@ template <typename T>
 __global__ __launch_bounds__(kTPB) void many_normest_kernel(ManyArgs<T> a, int it0, int nit) {
   __shared__ double red[2 * (kWaves + 1)];
   __shared__ T part[kTPB];
-  const int q = blockIdx.x, m = a.m, n = a.n;
+  const int q = blockIdx.x;
   ManyState<T> &st = a.st[q];
   if (it0 > 0 && st.ne_done) return;
-  T *w = a.ws + q * a.stride;
+  many_problem(a, q);
+  const int m = a.m, n = a.n;
+  T *w = a.ws;
   const T *A = w + a.oA;
   T *x = w + a.ox[kXtemp], *Sx = w + a.oy[kYtemp];
   T est = 0;
@@ -287,12 +352,18 @@ __global__ __launch_bounds__(kTPB) void many_normest_kernel(ManyArgs<T> a, int i
 // 4 x 4 per thread, summed over the long dimension in order.  grid (lower tiles, problems)
 template <typename T>
 __global__ __launch_bounds__(kTPB) void many_gram_kernel(ManyArgs<T> a) {
-  const int q = blockIdx.y, k = a.k, n = a.n;
-  int bi = 0;
+  const int q = blockIdx.y;
+  many_problem(a, q);
+  const int k = a.k, n = a.n;
   const int t = blockIdx.x;
+  // the grid covers the largest problem of the launch: a tile past this problem's own count has nothing to do (the
+  // kernel has no barrier, and the test is uniform over the workgroup)
+  const int nb = (k + 63) / 64;
+  if (t >= nb * (nb + 1) / 2) return;
+  int bi = 0;
   while ((bi + 1) * (bi + 2) / 2 <= t) ++bi;
   const int bj = t - bi * (bi + 1) / 2;
-  T *w = a.ws + q * a.stride;
+  T *w = a.ws;
   const T *A = w + a.oA;
   T *G = w + a.oW;
   const int i0 = bi * 64 + (threadIdx.x / 16) * 4, j0 = bj * 64 + (threadIdx.x % 16) * 4;
@@ -324,9 +395,11 @@ __global__ __launch_bounds__(kTPB) void many_gram_kernel(ManyArgs<T> a) {
 template <typename T>
 __global__ __launch_bounds__(kTPB) void many_factor_kernel(ManyArgs<T> a) {
   __shared__ T bc;
-  const int q = blockIdx.x, k = a.k;
+  const int q = blockIdx.x;
+  many_problem(a, q);
+  const int k = a.k;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  T *w = a.ws + q * a.stride;
+  T *w = a.ws;
   T *L = w + a.oW, *tmp = w + a.oT;
   for (int j = 0; j < k; ++j) {
     const T *lj = L + static_cast<size_t>(j) * k;
@@ -381,9 +454,12 @@ template <typename T>
 __global__ __launch_bounds__(kTPB) void many_loop_kernel(ManyArgs<T> a, int iters) {
   __shared__ double red[6 * (kWaves + 1)];
   __shared__ T part[kTPB];
-  const int q = blockIdx.x, m = a.m, n = a.n, k = a.k;
+  const int q = blockIdx.x;
   if (a.st[q].stopped) return;
-  T *w = a.ws + q * a.stride;
+  const int bound = many_problem(a, q);
+  iters = iters < bound ? iters : bound;
+  const int m = a.m, n = a.n, k = a.k;
+  T *w = a.ws;
   const T *A = w + a.oA, *W = w + a.oW;
   T *tv = w + a.oT;
   T *x = w + a.ox[kX], *xt = w + a.ox[kXt], *xprev = w + a.ox[kXprev], *x12 = w + a.ox[kX12];
@@ -509,14 +585,12 @@ __global__ __launch_bounds__(kTPB) void many_loop_kernel(ManyArgs<T> a, int iter
       wg_sum<2>(fv, red);
       const T nr = -rho;
       for (int i = threadIdx.x; i < m; i += kTPB) {
-        const size_t o = static_cast<size_t>(q) * m + i;
-        a.lo[o] = (((yt[i] - yprev[i]) + y12[i]) * nr) * d[i];
-        a.yo[o] = y12[i] / d[i];
+        a.lo[i] = (((yt[i] - yprev[i]) + y12[i]) * nr) * d[i];
+        a.yo[i] = y12[i] / d[i];
       }
       for (int j = threadIdx.x; j < n; j += kTPB) {
-        const size_t o = static_cast<size_t>(q) * n + j;
-        a.muo[o] = (((xt[j] - xprev[j]) + x12[j]) * nr) / e[j];
-        a.xo[o] = x12[j] * e[j];
+        a.muo[j] = (((xt[j] - xprev[j]) + x12[j]) * nr) / e[j];
+        a.xo[j] = x12[j] * e[j];
       }
       if (threadIdx.x == 0) {
         a.optval[q] = static_cast<double>(static_cast<T>(fv[0]) + static_cast<T>(fv[1]));
@@ -548,8 +622,10 @@ __global__ __launch_bounds__(kTPB) void many_loop_kernel(ManyArgs<T> a, int iter
 template <typename T>
 __global__ __launch_bounds__(kTPB) void many_begin_kernel(ManyArgs<T> a, const int *warm) {
   __shared__ T part[kTPB];
-  const int q = blockIdx.x, m = a.m, n = a.n;
-  T *w = a.ws + q * a.stride;
+  const int q = blockIdx.x;
+  many_problem(a, q);
+  const int m = a.m, n = a.n;
+  T *w = a.ws;
   const T *A = w + a.oA;
   T *x = w + a.ox[kX], *xt = w + a.ox[kXt], *y = w + a.oy[kY], *yt = w + a.oy[kYt], *ytemp = w + a.oy[kYtemp];
   const T *e = w + a.ox[kE], *d = w + a.oy[kD];
@@ -559,7 +635,7 @@ __global__ __launch_bounds__(kTPB) void many_begin_kernel(ManyArgs<T> a, const i
     for (int i = threadIdx.x; i < m; i += kTPB) { y[i] = 0; yt[i] = 0; }
     return;
   }
-  const T *x0 = a.xo + static_cast<size_t>(q) * n, *l0 = a.lo + static_cast<size_t>(q) * m;
+  const T *x0 = a.xo, *l0 = a.lo;
   const T mr = static_cast<T>(-1) / a.ctl[q].rho;
   for (int j = threadIdx.x; j < n; j += kTPB) x[j] = x0[j] / e[j];
   for (int i = threadIdx.x; i < m; i += kTPB) ytemp[i] = l0[i] / d[i];
@@ -587,19 +663,113 @@ size_t workspace_cap_bytes(int device) {
 // regularisers (equil_helper.h:152-153, 159-160).
 template <typename T>
 void many_layout(ManyArgs<T> &a, int ord, size_t m_, size_t n_) {
-  const int m = static_cast<int>(m_), n = static_cast<int>(n_), K = std::min(m, n);
-  auto R64 = [](size_t v) { return round_up(v, 64); };
-  a.m = m; a.n = n; a.k = K; a.tall = m > n;
+  many_offsets(a, static_cast<int>(m_), static_cast<int>(n_));
   a.rowmaj = ord == ROW_MAJ;
-  size_t off = 0;
-  a.oA = off; off += R64(m_ * n_);
-  a.oW = off; off += R64(static_cast<size_t>(K) * K);
-  a.oT = off; off += R64(K);
-  for (int v = 0; v < kNumX; ++v) { a.ox[v] = off; off += R64(n_); }
-  for (int v = 0; v < kNumY; ++v) { a.oy[v] = off; off += R64(m_); }
-  a.stride = off;
   a.ce = static_cast<T>(1e-4) * static_cast<T>(m_ + n_) / static_cast<T>(m_);
   a.cd = static_cast<T>(1e-4) * static_cast<T>(m_ + n_) / static_cast<T>(n_);
+}
+
+// ADMM iterations per loop launch: kMaxIterPerLaunch, fewer where an iteration streams much (kLaunchBytes).
+template <typename T>
+int many_iters_per_launch(size_t mn, int K) {
+  const double iter_bytes = (2.0 * static_cast<double>(mn) + static_cast<double>(K) * K) * sizeof(T);
+  return static_cast<int>(std::max(1.0, std::min<double>(kMaxIterPerLaunch, kLaunchBytes / iter_bytes)));
+}
+
+// The shapes of a call's k problems and where problem j starts in every packed array: rows (f, y, l), columns
+// (g, x, mu), matrix elements (A) and workspace elements.  Uniform: one (m, n), problem j at j times the size,
+// nothing stored per problem.  Ragged: the prefix sums of the k shapes.
+template <typename T>
+struct ManyShapes {
+  int k = 0;
+  bool ragged = false;
+  size_t m0 = 0, n0 = 0, stride0 = 0;          // uniform: the shape and its workspace stride; ragged: the largest m, n
+  std::vector<size_t> mv, nv, r0, c0, e0, w0;  // ragged: the shapes and the k + 1 prefix sums
+
+  void set_uniform(int kk, size_t m, size_t n) {
+    ManyArgs<T> a{};
+    many_offsets(a, static_cast<int>(m), static_cast<int>(n));
+    k = kk; ragged = false; m0 = m; n0 = n; stride0 = a.stride;
+  }
+  void set_ragged(int kk, const size_t *m, const size_t *n) {
+    const size_t kz = static_cast<size_t>(kk);
+    k = kk; ragged = true; m0 = 0; n0 = 0;
+    mv.assign(m, m + kz); nv.assign(n, n + kz);
+    r0.assign(kz + 1, 0); c0.assign(kz + 1, 0); e0.assign(kz + 1, 0); w0.assign(kz + 1, 0);
+    for (size_t j = 0; j < kz; ++j) {
+      ManyArgs<T> a{};
+      many_offsets(a, static_cast<int>(m[j]), static_cast<int>(n[j]));
+      r0[j + 1] = r0[j] + m[j]; c0[j + 1] = c0[j] + n[j]; e0[j + 1] = e0[j] + m[j] * n[j]; w0[j + 1] = w0[j] + a.stride;
+      m0 = std::max(m0, m[j]); n0 = std::max(n0, n[j]);
+    }
+  }
+  size_t m(size_t j) const { return ragged ? mv[j] : m0; }
+  size_t n(size_t j) const { return ragged ? nv[j] : n0; }
+  size_t row0(size_t j) const { return ragged ? r0[j] : j * m0; }
+  size_t col0(size_t j) const { return ragged ? c0[j] : j * n0; }
+  size_t el0(size_t j) const { return ragged ? e0[j] : j * m0 * n0; }
+  size_t ws0(size_t j) const { return ragged ? w0[j] : j * stride0; }
+  // the extent of problems [j0, j0 + cnt) in each packed array
+  size_t rows(size_t j0, size_t cnt) const { return row0(j0 + cnt) - row0(j0); }
+  size_t cols(size_t j0, size_t cnt) const { return col0(j0 + cnt) - col0(j0); }
+  size_t els(size_t j0, size_t cnt) const { return el0(j0 + cnt) - el0(j0); }
+  size_t wss(size_t j0, size_t cnt) const { return ws0(j0 + cnt) - ws0(j0); }
+  // the rows of the ragged table for problems [j0, j0 + cnt), offsets counted from problem `base`
+  void table(std::vector<ManyProb<T>> &t, size_t j0, size_t cnt, size_t base) const {
+    t.resize(cnt);
+    for (size_t q = 0; q < cnt; ++q) {
+      const size_t j = j0 + q, mj = mv[j], nj = nv[j];
+      ManyProb<T> &p = t[q];
+      p.m = static_cast<int>(mj); p.n = static_cast<int>(nj);
+      p.ipl = many_iters_per_launch<T>(mj * nj, static_cast<int>(std::min(mj, nj)));
+      p.pad = 0;
+      p.ws = w0[j] - w0[base]; p.src = e0[j] - e0[base]; p.xo = c0[j] - c0[base]; p.yo = r0[j] - r0[base];
+      p.ce = static_cast<T>(1e-4) * static_cast<T>(mj + nj) / static_cast<T>(mj);
+      p.cd = static_cast<T>(1e-4) * static_cast<T>(mj + nj) / static_cast<T>(nj);
+    }
+  }
+};
+
+// What the launches of problems [j0, j0 + cnt) are sized by: the largest matrix and the largest Gram order among
+// them, the fewest and the most ADMM iterations per loop launch, and their workspace extent.
+struct ManyExtent {
+  size_t mn_max = 0, ws_elems = 0;
+  int K_max = 0, ipl_min = kMaxIterPerLaunch, ipl_max = 1;
+};
+template <typename T>
+ManyExtent many_extent(const ManyShapes<T> &sh, size_t j0, size_t cnt) {
+  ManyExtent x;
+  x.ws_elems = sh.wss(j0, cnt);
+  for (size_t j = j0; j < j0 + (sh.ragged ? cnt : 1); ++j) {
+    const size_t mn = sh.m(j) * sh.n(j);
+    const int K = static_cast<int>(std::min(sh.m(j), sh.n(j)));
+    const int ipl = many_iters_per_launch<T>(mn, K);
+    x.mn_max = std::max(x.mn_max, mn);
+    x.K_max = std::max(x.K_max, K);
+    x.ipl_min = std::min(x.ipl_min, ipl);
+    x.ipl_max = std::max(x.ipl_max, ipl);
+  }
+  return x;
+}
+
+// Problems packed into chunks in order: a chunk takes problems while their bytes (per(j)) fit under cap and their
+// count under max_cnt, and holds at least one.  Returns the chunk starts and k.
+template <typename Per>
+std::vector<size_t> many_chunks(size_t k, size_t cap, size_t max_cnt, Per per) {
+  std::vector<size_t> starts{0};
+  size_t used = 0, cnt = 0;
+  for (size_t j = 0; j < k; ++j) {
+    const size_t b = per(j);
+    if (cnt > 0 && (used + b > cap || cnt >= max_cnt)) {
+      starts.push_back(j);
+      used = 0;
+      cnt = 0;
+    }
+    used += b;
+    ++cnt;
+  }
+  starts.push_back(k);
+  return starts;
 }
 
 // The Norm2Est start vector (n values) into rnd.
@@ -614,10 +784,12 @@ void many_start_vector(T *rnd, size_t n, hipStream_t s) {
 // The setup of the cnt problems of a chunk (a: many_layout's fields, ws, st, src and rnd set): zero workspaces and
 // states, then copy, all 50 Sinkhorn-Knopp passes, scale, norm estimate, Gram tiles, factor and W = L^-1.  Returns the
 // number of launches.  The solve and PogsAmdManySetupCheck both run this sequence.
+// x: the problems' extent (many_extent); the launches are cut by the largest matrix and the Gram grid covers the
+// largest order.  ws0: where the cnt workspaces start (a.ws for a uniform chunk).
 template <typename T>
-unsigned long long many_setup(const ManyArgs<T> &a, int cnt, hipStream_t s) {
-  const size_t mn = static_cast<size_t>(a.m) * a.n;
-  const int K = a.k;
+unsigned long long many_setup(const ManyArgs<T> &a, int cnt, const ManyExtent &x, T *ws0, hipStream_t s) {
+  const size_t mn = x.mn_max;
+  const int K = x.K_max;
   const double pass_bytes = 2.0 * static_cast<double>(mn) * sizeof(T);
   const int per_launch = static_cast<int>(std::max(1.0, std::min(50.0, kLaunchBytes / pass_bytes)));
   const int nb = (K + 63) / 64, ntiles = nb * (nb + 1) / 2;
@@ -625,7 +797,7 @@ unsigned long long many_setup(const ManyArgs<T> &a, int cnt, hipStream_t s) {
   unsigned long long launches = 0;
   POGS_HIP_CHECK(hipMemsetAsync(a.st, 0, static_cast<size_t>(cnt) * sizeof(ManyState<T>), s));
   // zero work vectors: the cold start (z = zt = 0)
-  POGS_HIP_CHECK(hipMemsetAsync(a.ws, 0, static_cast<size_t>(cnt) * a.stride * sizeof(T), s));
+  POGS_HIP_CHECK(hipMemsetAsync(ws0, 0, x.ws_elems * sizeof(T), s));
   hipLaunchKernelGGL(many_copy_kernel<T>, dim3(copy_blocks, cnt), dim3(kTPB), 0, s, a);
   ++launches;
   for (int p0 = 0; p0 < 50; p0 += per_launch) {
@@ -666,7 +838,9 @@ void many_setup_check_t(int ord, int kk, size_t m_, size_t n_, const void *Ain, 
     src = stage.p;
   }
   a.ws = ws.p; a.rnd = rnd.p; a.st = st.p; a.src = src;
-  many_setup(a, kk, s);
+  ManyShapes<T> sh;
+  sh.set_uniform(kk, m_, n_);
+  many_setup(a, kk, many_extent(sh, 0, kk), ws.p, s);
   std::vector<ManyState<T>> hst(kk);
   POGS_HIP_CHECK(hipMemcpyAsync(hst.data(), st.p, static_cast<size_t>(kk) * sizeof(ManyState<T>), hipMemcpyDeviceToHost,
                                 s));
@@ -685,13 +859,6 @@ void many_setup_check_t(int ord, int kk, size_t m_, size_t n_, const void *Ain, 
     for (int q = 0; q < kk; ++q) nrmA[q] = static_cast<double>(hst[q].nrmA);
 }
 
-// ADMM iterations per loop launch: kMaxIterPerLaunch, fewer where an iteration streams much (kLaunchBytes).
-template <typename T>
-int many_iters_per_launch(size_t mn, int K) {
-  const double iter_bytes = (2.0 * static_cast<double>(mn) + static_cast<double>(K) * K) * sizeof(T);
-  return static_cast<int>(std::max(1.0, std::min<double>(kMaxIterPerLaunch, kLaunchBytes / iter_bytes)));
-}
-
 // The functions of cnt problems on their way to the device: per-element fields packed into one upload (tpool, hpool),
 // broadcast fields as values.  The host copies live here until the next run.
 template <typename T>
@@ -699,15 +866,15 @@ struct ManyFnUpload {
   std::vector<T> tp;
   std::vector<int> hp;
   std::vector<ManyFn<T>> fh;
-  void run(const FnHost *f, const FnHost *g, int cnt, size_t m_, size_t n_, T *tpool, int *hpool, ManyFn<T> *fnd,
-           hipStream_t s) {
+  void run(const FnHost *f, const FnHost *g, const ManyShapes<T> &sh, size_t j0, int cnt, T *tpool, int *hpool,
+           ManyFn<T> *fnd, hipStream_t s) {
     tp.clear();
     hp.clear();
     fh.resize(2 * static_cast<size_t>(cnt));
     for (int q = 0; q < cnt; ++q) {
       for (int side = 0; side < 2; ++side) {
-        const FnHost &fn = side == 0 ? f[q] : g[q];
-        const size_t len = side == 0 ? m_ : n_;
+        const FnHost &fn = side == 0 ? f[j0 + q] : g[j0 + q];
+        const size_t len = side == 0 ? sh.m(j0 + q) : sh.n(j0 + q);
         warn_negative_coeffs<T>(fn, len);
         ManyFn<T> &d = fh[2 * q + side];
         const void *ptr[5] = {fn.a, fn.b, fn.c, fn.d, fn.e};
@@ -736,14 +903,16 @@ struct ManyFnUpload {
 };
 
 // The loop of cnt problems (a.done_count zeroed on the stream before): every launch advances each live problem by at
-// most ipl iterations, and the host reads one done-count per launch.  Returns the number of launches.
+// most its own iterations per launch (x.ipl_max is the launch's bound, a ragged problem's table row may lower it;
+// x.ipl_min bounds the number of launches), and the host reads one done-count per launch.  Returns the number of
+// launches.
 template <typename T>
-unsigned long long many_run_loop(const ManyArgs<T> &a, int cnt, int ipl, unsigned max_iter, unsigned *hdone,
-                                 hipStream_t s) {
-  const unsigned long long max_launches = (max_iter + ipl - 1) / ipl + 1;
+unsigned long long many_run_loop(const ManyArgs<T> &a, int cnt, const ManyExtent &x, unsigned max_iter,
+                                 unsigned *hdone, hipStream_t s) {
+  const unsigned long long max_launches = (max_iter + x.ipl_min - 1) / x.ipl_min + 1;
   unsigned long long nl = 0;
   for (;;) {
-    hipLaunchKernelGGL(many_loop_kernel<T>, dim3(cnt), dim3(kTPB), 0, s, a, ipl);
+    hipLaunchKernelGGL(many_loop_kernel<T>, dim3(cnt), dim3(kTPB), 0, s, a, x.ipl_max);
     POGS_HIP_CHECK(hipGetLastError());
     ++nl;
     POGS_HIP_CHECK(hipMemcpyAsync(hdone, a.done_count, sizeof(unsigned), hipMemcpyDeviceToHost, s));
@@ -773,86 +942,125 @@ inline void many_print_summary(const char *head, int k, const unsigned *final_it
   std::fflush(stdout);
 }
 
+// "of 500 x 300" or, ragged, "of 310..700 x 300..300": the shapes in a summary line.
 template <typename T>
-void solve_many_t(int ord, int kk, size_t m_, size_t n_, const void *Ain, int mem, int device, const FnHost *f,
+void many_shape_text(char *buf, size_t len, const ManyShapes<T> &sh) {
+  if (!sh.ragged) {
+    std::snprintf(buf, len, "%zu x %zu", sh.m0, sh.n0);
+    return;
+  }
+  std::snprintf(buf, len, "%zu..%zu x %zu..%zu", *std::min_element(sh.mv.begin(), sh.mv.end()), sh.m0,
+                *std::min_element(sh.nv.begin(), sh.nv.end()), sh.n0);
+}
+
+// The one-shot solve of the sh.k problems, uniform or ragged, in chunks under the workspace cap.
+template <typename T>
+void solve_many_t(int ord, const ManyShapes<T> &sh, const void *Ain, int mem, int device, const FnHost *f,
                   const FnHost *g, const double *rho0, const SolveParams &p, const BatchOut &out) {
   const double t0 = wall_s();
   Ctx ctx;
   ctx.init(device, 0);
   hipStream_t s = ctx.stream;
-  const int m = static_cast<int>(m_), n = static_cast<int>(n_), K = std::min(m, n);
-  const size_t mn = m_ * n_;
+  const size_t kz = static_cast<size_t>(sh.k);
   ManyArgs<T> a{};
-  many_layout(a, ord, m_, n_);
-  // per problem: workspace, staged input, outputs, coefficient arrays, control
-  const size_t per = sizeof(T) * (a.stride + (mem == POGS_AMD_HOST ? mn : 0) + 2 * (m_ + n_) + 5 * (m_ + n_)) +
-                     sizeof(int) * (m_ + n_) + sizeof(AdmmControl<T>) + sizeof(ManyState<T>) + 64;
-  const size_t cap = workspace_cap_bytes(ctx.device);
-  const int chunk = static_cast<int>(std::max<size_t>(1, std::min<size_t>(static_cast<size_t>(kk), cap / per)));
+  many_layout(a, ord, sh.m0, sh.n0);   // ragged: every kernel replaces the shape fields by the problem's own
+  // per problem: workspace, staged input, outputs, coefficient arrays, control (and its row of the ragged table)
+  auto per = [&](size_t j) {
+    const size_t len = sh.m(j) + sh.n(j);
+    return sizeof(T) * (sh.wss(j, 1) + (mem == POGS_AMD_HOST ? sh.els(j, 1) : 0) + 2 * len + 5 * len) +
+           sizeof(int) * len + sizeof(AdmmControl<T>) + sizeof(ManyState<T>) + 64 +
+           (sh.ragged ? sizeof(ManyProb<T>) : 0);
+  };
+  const std::vector<size_t> starts = many_chunks(kz, workspace_cap_bytes(ctx.device), kz, per);
+  // every buffer holds the largest chunk
+  size_t chunk = 0, ws_e = 0, st_e = 0, rows = 0, cols = 0;
+  for (size_t c = 0; c + 1 < starts.size(); ++c) {
+    const size_t j0 = starts[c], cnt = starts[c + 1] - j0;
+    chunk = std::max(chunk, cnt);
+    ws_e = std::max(ws_e, sh.wss(j0, cnt));
+    st_e = std::max(st_e, sh.els(j0, cnt));
+    rows = std::max(rows, sh.rows(j0, cnt));
+    cols = std::max(cols, sh.cols(j0, cnt));
+    if (!sh.ragged) break;   // uniform: the first chunk is the largest
+  }
 
-  DevBuf<T> ws(static_cast<size_t>(chunk) * a.stride), stage, rnd(n_);
-  if (mem == POGS_AMD_HOST) stage.alloc(static_cast<size_t>(chunk) * mn);
-  DevBuf<T> xo(static_cast<size_t>(chunk) * n_), yo(static_cast<size_t>(chunk) * m_), lo(static_cast<size_t>(chunk) * m_),
-      muo(static_cast<size_t>(chunk) * n_);
+  DevBuf<T> ws(ws_e), stage, rnd(sh.n0);
+  if (mem == POGS_AMD_HOST) stage.alloc(st_e);
+  DevBuf<T> xo(cols), yo(rows), lo(rows), muo(cols);
   DevBuf<double> optv(chunk);
   DevBuf<unsigned> iters(chunk), done(1);
   DevBuf<int> stat(chunk);
-  DevBuf<ManyFn<T>> fnd(2 * static_cast<size_t>(chunk));
+  DevBuf<ManyFn<T>> fnd(2 * chunk);
   DevBuf<AdmmControl<T>> ctld(chunk);
   DevBuf<ManyState<T>> std_(chunk);
-  DevBuf<T> tpool(static_cast<size_t>(chunk) * 5 * (m_ + n_) + 1);
-  DevBuf<int> hpool(static_cast<size_t>(chunk) * (m_ + n_) + 1);
+  DevBuf<T> tpool(5 * (rows + cols) + 1);
+  DevBuf<int> hpool(rows + cols + 1);
+  DevBuf<ManyProb<T>> probd;
+  if (sh.ragged) probd.alloc(chunk);
   PinnedBuf<unsigned> hdone(1);
-  many_start_vector(rnd.p, n_, s);
+  // the start vector of the widest problem: a narrower one reads its first n values, which are what it gets alone
+  many_start_vector(rnd.p, sh.n0, s);
   a.ws = ws.p; a.rnd = rnd.p; a.fn = fnd.p; a.ctl = ctld.p; a.st = std_.p; a.done_count = done.p;
   a.xo = xo.p; a.yo = yo.p; a.lo = lo.p; a.muo = muo.p; a.optval = optv.p; a.iters = iters.p; a.status = stat.p;
-
-  const int ipl = many_iters_per_launch<T>(mn, K);
+  a.prob = probd.p;
 
   ManyFnUpload<T> up;
   std::vector<AdmmControl<T>> ch(chunk);
+  std::vector<ManyProb<T>> tab;
   unsigned long long launches = 0;
   double t_setup = 0, t_loop = 0;
-  for (int j0 = 0; j0 < kk; j0 += chunk) {
-    const int cnt = std::min(chunk, kk - j0);
+  for (size_t c = 0; c + 1 < starts.size(); ++c) {
+    const size_t j0 = starts[c];
+    const int cnt = static_cast<int>(starts[c + 1] - j0);
+    const ManyExtent ext = many_extent(sh, j0, cnt);
     const double tc0 = wall_s();
-    const T *src = static_cast<const T *>(Ain) + static_cast<size_t>(j0) * mn;
+    const T *src = static_cast<const T *>(Ain) + sh.el0(j0);
     if (mem == POGS_AMD_HOST) {
-      POGS_HIP_CHECK(hipMemcpyAsync(stage.p, src, static_cast<size_t>(cnt) * mn * sizeof(T), hipMemcpyHostToDevice, s));
+      POGS_HIP_CHECK(hipMemcpyAsync(stage.p, src, sh.els(j0, cnt) * sizeof(T), hipMemcpyHostToDevice, s));
       src = stage.p;
     }
     a.src = src;
-    up.run(f + j0, g + j0, cnt, m_, n_, tpool.p, hpool.p, fnd.p, s);
-    for (int q = 0; q < cnt; ++q) ch[q] = make_admm_control<T>(p, rho0 ? rho0[j0 + q] : 1.0, m_, n_);
+    if (sh.ragged) {
+      sh.table(tab, j0, cnt, j0);
+      POGS_HIP_CHECK(hipMemcpyAsync(probd.p, tab.data(), tab.size() * sizeof(ManyProb<T>), hipMemcpyHostToDevice, s));
+    }
+    up.run(f, g, sh, j0, cnt, tpool.p, hpool.p, fnd.p, s);
+    for (int q = 0; q < cnt; ++q)
+      ch[q] = make_admm_control<T>(p, rho0 ? rho0[j0 + q] : 1.0, sh.m(j0 + q), sh.n(j0 + q));
     POGS_HIP_CHECK(hipMemcpyAsync(ctld.p, ch.data(), static_cast<size_t>(cnt) * sizeof(AdmmControl<T>),
                                   hipMemcpyHostToDevice, s));
     POGS_HIP_CHECK(hipMemsetAsync(done.p, 0, sizeof(unsigned), s));
-    launches += many_setup(a, cnt, s);
+    launches += many_setup(a, cnt, ext, ws.p, s);
     ctx.sync();
     const double tc1 = wall_s();
     t_setup += tc1 - tc0;
-    // the loop: every launch advances each live problem by at most ipl iterations
-    launches += many_run_loop(a, cnt, ipl, p.max_iter, hdone.p, s);
+    // the loop: every launch advances each live problem by at most its iterations per launch
+    launches += many_run_loop(a, cnt, ext, p.max_iter, hdone.p, s);
     t_loop += wall_s() - tc1;
     // outputs of the chunk
     auto d2h = [&](void *dst, const void *srcd, size_t bytes) {
       POGS_HIP_CHECK(hipMemcpyAsync(dst, srcd, bytes, hipMemcpyDeviceToHost, s));
     };
-    const size_t xb = static_cast<size_t>(cnt) * n_ * sizeof(T), yb = static_cast<size_t>(cnt) * m_ * sizeof(T);
-    d2h(static_cast<T *>(out.x) + static_cast<size_t>(j0) * n_, xo.p, xb);
-    if (out.y) d2h(static_cast<T *>(out.y) + static_cast<size_t>(j0) * m_, yo.p, yb);
-    if (out.l) d2h(static_cast<T *>(out.l) + static_cast<size_t>(j0) * m_, lo.p, yb);
-    if (out.mu) d2h(static_cast<T *>(out.mu) + static_cast<size_t>(j0) * n_, muo.p, xb);
+    const size_t xb = sh.cols(j0, cnt) * sizeof(T), yb = sh.rows(j0, cnt) * sizeof(T);
+    d2h(static_cast<T *>(out.x) + sh.col0(j0), xo.p, xb);
+    if (out.y) d2h(static_cast<T *>(out.y) + sh.row0(j0), yo.p, yb);
+    if (out.l) d2h(static_cast<T *>(out.l) + sh.row0(j0), lo.p, yb);
+    if (out.mu) d2h(static_cast<T *>(out.mu) + sh.col0(j0), muo.p, xb);
     if (out.optval) d2h(out.optval + j0, optv.p, cnt * sizeof(double));
     d2h(out.final_iter + j0, iters.p, cnt * sizeof(unsigned));
     d2h(out.status + j0, stat.p, cnt * sizeof(int));
     POGS_HIP_CHECK(hipStreamSynchronize(s));
   }
   if (p.verbose > 0) {
-    char head[160];
-    std::snprintf(head, sizeof(head), "POGS-AMD many: %d problems of %d x %d (%s), %d per chunk", kk, m, n,
-                  sizeof(T) == 8 ? "fp64" : "fp32", chunk);
-    many_print_summary(head, kk, out.final_iter, out.status, t_setup, t_loop, wall_s() - t0, launches);
+    char head[200], shape[96];
+    many_shape_text(shape, sizeof(shape), sh);
+    if (sh.ragged)
+      std::snprintf(head, sizeof(head), "POGS-AMD many: %d ragged problems of %s (%s), %zu chunks of at most %zu", sh.k,
+                    shape, sizeof(T) == 8 ? "fp64" : "fp32", starts.size() - 1, chunk);
+    else
+      std::snprintf(head, sizeof(head), "POGS-AMD many: %d problems of %s (%s), %zu per chunk", sh.k, shape,
+                    sizeof(T) == 8 ? "fp64" : "fp32", chunk);
+    many_print_summary(head, sh.k, out.final_iter, out.status, t_setup, t_loop, wall_s() - t0, launches);
   }
 }
 
@@ -862,59 +1070,87 @@ void solve_many_t(int ord, int kk, size_t m_, size_t n_, const void *Ain, int me
 template <typename T>
 class ManyHandleT : public ManyHandle {
  public:
-  ManyHandleT(int ord, int kk, size_t m, size_t n, const void *Ain, int mem, int device) : k_(kk), m_(m), n_(n) {
+  ManyHandleT(int ord, ManyShapes<T> &&shapes, const void *Ain, int mem, int device)
+      : sh_(std::move(shapes)), k_(sh_.k) {
     const double t0 = wall_s();
     ctx_.init(device, 0);
     hipStream_t s = ctx_.stream;
-    many_layout(a_, ord, m, n);
-    const size_t kz = static_cast<size_t>(kk), mn = m * n, len = m + n;
+    many_layout(a_, ord, sh_.m0, sh_.n0);   // ragged: every kernel replaces the shape fields by the problem's own
+    const size_t kz = static_cast<size_t>(k_);
+    const size_t rows = sh_.rows(0, kz), cols = sh_.cols(0, kz), len = rows + cols, ws_e = sh_.wss(0, kz);
     std::memset(&info_, 0, sizeof(info_));
-    info_.k = kk; info_.dtype = sizeof(T) == 8 ? POGS_AMD_F64 : POGS_AMD_F32; info_.m = m; info_.n = n;
-    info_.resident_bytes = kz * (sizeof(T) * (a_.stride + 2 * len + 5 * len + 1) + sizeof(int) * (len + 2) +
-                                 sizeof(double) + sizeof(unsigned) + 2 * sizeof(ManyFn<T>) + sizeof(AdmmControl<T>) +
-                                 sizeof(ManyState<T>));
+    info_.k = k_; info_.dtype = sizeof(T) == 8 ? POGS_AMD_F64 : POGS_AMD_F32; info_.m = sh_.m0; info_.n = sh_.n0;
+    info_.resident_bytes = sizeof(T) * (ws_e + 2 * len + 5 * len + kz) + sizeof(int) * (len + 2 * kz) +
+                           kz * (sizeof(double) + sizeof(unsigned) + 2 * sizeof(ManyFn<T>) + sizeof(AdmmControl<T>) +
+                                 sizeof(ManyState<T>) + (sh_.ragged ? sizeof(ManyProb<T>) : 0));
     try {
-      ws_.alloc(kz * a_.stride);
-      xo_.alloc(kz * n); yo_.alloc(kz * m); lo_.alloc(kz * m); muo_.alloc(kz * n);
+      ws_.alloc(ws_e);
+      xo_.alloc(cols); yo_.alloc(rows); lo_.alloc(rows); muo_.alloc(cols);
       optv_.alloc(kz); iters_.alloc(kz); stat_.alloc(kz); warm_.alloc(kz); done_.alloc(1);
       fnd_.alloc(2 * kz); ctld_.alloc(kz); st_.alloc(kz);
-      tpool_.alloc(kz * 5 * len + 1); hpool_.alloc(kz * len + 1);
+      tpool_.alloc(5 * len + 1); hpool_.alloc(len + 1);
+      if (sh_.ragged) prob_.alloc(kz);
     } catch (const std::exception &e) {
       (void)hipGetLastError();
-      char buf[512];
+      char buf[512], shape[96];
+      many_shape_text(shape, sizeof(shape), sh_);
       std::snprintf(buf, sizeof(buf),
-                    "many-problem handle: the resident footprint of %d problems of %zu x %zu (%.1f MB) cannot be "
+                    "many-problem handle: the resident footprint of %d problems of %s (%.1f MB) cannot be "
                     "allocated; PogsAmdSolveManyFn solves them in chunks [%s]",
-                    kk, m, n, static_cast<double>(info_.resident_bytes) / (1 << 20), e.what());
+                    k_, shape, static_cast<double>(info_.resident_bytes) / (1 << 20), e.what());
       throw Error(buf);
     }
     hdone_.alloc(1);
     a_.ws = ws_.p; a_.fn = fnd_.p; a_.ctl = ctld_.p; a_.st = st_.p; a_.done_count = done_.p;
     a_.xo = xo_.p; a_.yo = yo_.p; a_.lo = lo_.p; a_.muo = muo_.p; a_.optval = optv_.p; a_.iters = iters_.p;
     a_.status = stat_.p;
+    a_.prob = prob_.p;
+    if (sh_.ragged) {
+      // the handle's table counts every offset from problem 0: the pools' base pointers are the handle's buffers
+      std::vector<ManyProb<T>> tab;
+      sh_.table(tab, 0, kz, 0);
+      POGS_HIP_CHECK(hipMemcpyAsync(prob_.p, tab.data(), kz * sizeof(ManyProb<T>), hipMemcpyHostToDevice, s));
+      POGS_HIP_CHECK(hipStreamSynchronize(s));
+    }
     // setup in chunks: a host A through a staging buffer under the workspace cap; a chunk is also the y extent of
     // the copy and Gram grids
-    size_t chunk = std::min<size_t>(kz, 32768);
-    if (mem == POGS_AMD_HOST)
-      chunk = std::max<size_t>(1, std::min(chunk, workspace_cap_bytes(ctx_.device) / (mn * sizeof(T))));
-    DevBuf<T> stage, rnd(n);
-    if (mem == POGS_AMD_HOST) stage.alloc(chunk * mn);
-    many_start_vector(rnd.p, n, s);
-    for (size_t j0 = 0; j0 < kz; j0 += chunk) {
-      const int cnt = static_cast<int>(std::min(chunk, kz - j0));
+    const size_t cap = mem == POGS_AMD_HOST ? workspace_cap_bytes(ctx_.device) : ~static_cast<size_t>(0);
+    const std::vector<size_t> starts = many_chunks(kz, cap, 32768, [&](size_t j) {
+      return mem == POGS_AMD_HOST ? sh_.els(j, 1) * sizeof(T) : static_cast<size_t>(0);
+    });
+    DevBuf<T> stage, rnd(sh_.n0);
+    if (mem == POGS_AMD_HOST) {
+      size_t st_e = 0;
+      for (size_t c = 0; c + 1 < starts.size(); ++c) st_e = std::max(st_e, sh_.els(starts[c], starts[c + 1] - starts[c]));
+      stage.alloc(st_e);
+    }
+    many_start_vector(rnd.p, sh_.n0, s);
+    for (size_t ci = 0; ci + 1 < starts.size(); ++ci) {
+      const size_t j0 = starts[ci];
+      const int cnt = static_cast<int>(starts[ci + 1] - j0);
+      const T *src = static_cast<const T *>(Ain) + sh_.el0(j0);
+      if (mem == POGS_AMD_HOST) {
+        POGS_HIP_CHECK(hipMemcpyAsync(stage.p, src, sh_.els(j0, cnt) * sizeof(T), hipMemcpyHostToDevice, s));
+        src = stage.p;
+      }
+      // the chunk's problems are q = 0 .. cnt - 1 of this launch.  Uniform: the bases move to the chunk.  Ragged: the
+      // table rows move, their offsets still count from problem 0, so ws stays, and src0 says that src points at the
+      // chunk's first matrix
       ManyArgs<T> c = a_;
-      c.ws = ws_.p + j0 * a_.stride;
       c.st = st_.p + j0;
       c.rnd = rnd.p;
-      c.src = static_cast<const T *>(Ain) + j0 * mn;
-      if (mem == POGS_AMD_HOST) {
-        POGS_HIP_CHECK(hipMemcpyAsync(stage.p, c.src, static_cast<size_t>(cnt) * mn * sizeof(T), hipMemcpyHostToDevice, s));
-        c.src = stage.p;
+      if (sh_.ragged) {
+        c.prob = prob_.p + j0;
+        c.src = src;
+        c.src0 = sh_.el0(j0);
+      } else {
+        c.ws = ws_.p + sh_.ws0(j0);
+        c.src = src;
       }
-      many_setup(c, cnt, s);
+      many_setup(c, cnt, many_extent(sh_, j0, cnt), ws_.p + sh_.ws0(j0), s);
     }
     ctx_.sync();
-    ipl_ = many_iters_per_launch<T>(mn, a_.k);
+    ext_ = many_extent(sh_, 0, kz);
     last_status_.assign(kz, POGS_ERROR);
     last_rho_.assign(kz, 1.0);
     info_.setup_s = wall_s() - t0;
@@ -924,6 +1160,12 @@ class ManyHandleT : public ManyHandle {
   int device() const override { return ctx_.device; }
   int count() const override { return k_; }
   PogsAmdManyInfo info() const override { return info_; }
+  void shapes(size_t *m, size_t *n) const override {
+    for (size_t j = 0; j < static_cast<size_t>(k_); ++j) {
+      m[j] = sh_.m(j);
+      n[j] = sh_.n(j);
+    }
+  }
 
   void solve(const FnHost *f, const FnHost *g, const ManyStart &sa, const SolveParams &p, const BatchOut &out) override {
     POGS_CHECK(out.x && out.final_iter && out.status, "many-problem handle: x, final_iter and status must not be NULL");
@@ -936,8 +1178,8 @@ class ManyHandleT : public ManyHandle {
     const double t0 = wall_s();
     hipStream_t s = ctx_.stream;
     const size_t kz = static_cast<size_t>(k_);
-    const size_t xb = kz * n_ * sizeof(T), yb = kz * m_ * sizeof(T);
-    up_.run(f, g, k_, m_, n_, tpool_.p, hpool_.p, fnd_.p, s);
+    const size_t xb = sh_.cols(0, kz) * sizeof(T), yb = sh_.rows(0, kz) * sizeof(T);
+    up_.run(f, g, sh_, 0, k_, tpool_.p, hpool_.p, fnd_.p, s);
     ch_.resize(kz);
     hwarm_.resize(kz);
     for (size_t q = 0; q < kz; ++q) {
@@ -945,7 +1187,7 @@ class ManyHandleT : public ManyHandle {
       hwarm_[q] = sa.start == POGS_AMD_MANY_WARM_GIVEN || (sa.start == POGS_AMD_MANY_WARM_LAST && kept);
       double rho = sa.rho ? sa.rho[q] : 1.0;
       if (sa.start == POGS_AMD_MANY_WARM_LAST) rho = !kept ? 1.0 : sa.rho ? sa.rho[q] : last_rho_[q];
-      ch_[q] = make_admm_control<T>(p, rho, m_, n_);
+      ch_[q] = make_admm_control<T>(p, rho, sh_.m(q), sh_.n(q));
     }
     POGS_HIP_CHECK(hipMemcpyAsync(ctld_.p, ch_.data(), kz * sizeof(AdmmControl<T>), hipMemcpyHostToDevice, s));
     const int *warm = nullptr;
@@ -962,7 +1204,7 @@ class ManyHandleT : public ManyHandle {
     const double t1 = wall_s();
     hipLaunchKernelGGL(many_begin_kernel<T>, dim3(k_), dim3(kTPB), 0, s, a_, warm);
     POGS_HIP_CHECK(hipGetLastError());
-    const unsigned long long launches = 1 + many_run_loop(a_, k_, ipl_, p.max_iter, hdone_.p, s);
+    const unsigned long long launches = 1 + many_run_loop(a_, k_, ext_, p.max_iter, hdone_.p, s);
     const double t_loop = wall_s() - t1;
     auto d2h = [&](void *dst, const void *srcd, size_t bytes) {
       POGS_HIP_CHECK(hipMemcpyAsync(dst, srcd, bytes, hipMemcpyDeviceToHost, s));
@@ -989,19 +1231,22 @@ class ManyHandleT : public ManyHandle {
     info_.problem_iters = piters;
     if (p.verbose > 0) {
       static const char *const kStart[3] = {"cold", "warm (given)", "warm (last)"};
-      char head[200];
-      std::snprintf(head, sizeof(head), "POGS-AMD many handle: %d problems of %d x %d (%s), start %s", k_,
-                    static_cast<int>(m_), static_cast<int>(n_), sizeof(T) == 8 ? "fp64" : "fp32", kStart[sa.start]);
+      char head[240], shape[96];
+      many_shape_text(shape, sizeof(shape), sh_);
+      std::snprintf(head, sizeof(head), "POGS-AMD many handle: %d %sproblems of %s (%s), start %s", k_,
+                    sh_.ragged ? "ragged " : "", shape, sizeof(T) == 8 ? "fp64" : "fp32", kStart[sa.start]);
       many_print_summary(head, k_, out.final_iter, out.status, 0.0, t_loop, wall_s() - t0, launches);
     }
   }
 
  private:
+  ManyShapes<T> sh_;
+  int k_;
   Ctx ctx_;
   ManyArgs<T> a_{};
-  int k_, ipl_ = 1;
-  size_t m_, n_;
+  ManyExtent ext_;
   DevBuf<T> ws_, xo_, yo_, lo_, muo_, tpool_;
+  DevBuf<ManyProb<T>> prob_;               // ragged: the table, offsets from problem 0
   DevBuf<double> optv_;
   DevBuf<unsigned> iters_, done_;
   DevBuf<int> stat_, hpool_, warm_;
@@ -1030,19 +1275,82 @@ void many_check_args(int dtype, int ord, int k, size_t m, size_t n, const void *
   POGS_CHECK(std::max(m, n) <= POGS_AMD_MANY_MAX_DIM_MAX, "many-problem solve: max(m, n) exceeds POGS_AMD_MANY_MAX_DIM_MAX");
 }
 
+void many_check_ragged(int dtype, int ord, int k, const size_t *m, const size_t *n, const void *A, int mem) {
+  POGS_CHECK(dtype == POGS_AMD_F32 || dtype == POGS_AMD_F64, "ragged many-problem solve: unknown dtype");
+  POGS_CHECK(k >= 1, "ragged many-problem solve: k must be >= 1");
+  POGS_CHECK(ord == ROW_MAJ || ord == COL_MAJ, "ragged many-problem solve: unknown ord");
+  POGS_CHECK(mem == POGS_AMD_HOST || mem == POGS_AMD_DEVICE, "ragged many-problem solve: unknown mem");
+  POGS_CHECK(m != nullptr && n != nullptr, "ragged many-problem solve: null m or n");
+  POGS_CHECK(A != nullptr, "ragged many-problem solve: null A");
+  for (int j = 0; j < k; ++j) {
+    const char *why = m[j] < 1 || n[j] < 1 ? "m and n must be >= 1"
+                      : std::min(m[j], n[j]) > POGS_AMD_MANY_MIN_DIM_MAX ? "min(m, n) exceeds POGS_AMD_MANY_MIN_DIM_MAX"
+                      : std::max(m[j], n[j]) > POGS_AMD_MANY_MAX_DIM_MAX ? "max(m, n) exceeds POGS_AMD_MANY_MAX_DIM_MAX"
+                                                                          : nullptr;
+    if (why) {
+      char buf[256];
+      std::snprintf(buf, sizeof(buf), "ragged many-problem solve: problem %d of %d (m[%d] = %zu, n[%d] = %zu): %s", j, k,
+                    j, m[j], j, n[j], why);
+      throw Error(buf);
+    }
+  }
+}
+
+namespace {
+template <typename T>
+ManyHandle *many_new_handle(int ord, int k, size_t m, size_t n, const size_t *mv, const size_t *nv, const void *A,
+                            int mem, int device) {
+  ManyShapes<T> sh;
+  if (mv) sh.set_ragged(k, mv, nv);
+  else sh.set_uniform(k, m, n);
+  return new ManyHandleT<T>(ord, std::move(sh), A, mem, device);
+}
+}  // namespace
+
 ManyHandle *many_create(int dtype, int ord, int k, size_t m, size_t n, const void *A, int mem, int device) {
   many_check_args(dtype, ord, k, m, n, A, mem);
   DeviceGuard guard(device);
-  if (dtype == POGS_AMD_F64) return new ManyHandleT<double>(ord, k, m, n, A, mem, device);
-  return new ManyHandleT<float>(ord, k, m, n, A, mem, device);
+  if (dtype == POGS_AMD_F64) return many_new_handle<double>(ord, k, m, n, nullptr, nullptr, A, mem, device);
+  return many_new_handle<float>(ord, k, m, n, nullptr, nullptr, A, mem, device);
+}
+
+ManyHandle *many_create_ragged(int dtype, int ord, int k, const size_t *m, const size_t *n, const void *A, int mem,
+                               int device) {
+  many_check_ragged(dtype, ord, k, m, n, A, mem);
+  DeviceGuard guard(device);
+  if (dtype == POGS_AMD_F64) return many_new_handle<double>(ord, k, 0, 0, m, n, A, mem, device);
+  return many_new_handle<float>(ord, k, 0, 0, m, n, A, mem, device);
+}
+
+void solve_many_ragged(int dtype, int ord, int k, const size_t *m, const size_t *n, const void *A, int mem, int device,
+                       const FnHost *f, const FnHost *g, const double *rho, const SolveParams &p, const BatchOut &out) {
+  many_check_ragged(dtype, ord, k, m, n, A, mem);
+  POGS_CHECK(out.x && out.final_iter && out.status,
+             "ragged many-problem solve: x, final_iter and status must not be NULL");
+  if (dtype == POGS_AMD_F64) {
+    ManyShapes<double> sh;
+    sh.set_ragged(k, m, n);
+    solve_many_t<double>(ord, sh, A, mem, device, f, g, rho, p, out);
+  } else {
+    ManyShapes<float> sh;
+    sh.set_ragged(k, m, n);
+    solve_many_t<float>(ord, sh, A, mem, device, f, g, rho, p, out);
+  }
 }
 
 void solve_many(int dtype, int ord, int k, size_t m, size_t n, const void *A, int mem, int device, const FnHost *f,
                 const FnHost *g, const double *rho, const SolveParams &p, const BatchOut &out) {
   many_check_args(dtype, ord, k, m, n, A, mem);
   POGS_CHECK(out.x && out.final_iter && out.status, "many-problem solve: x, final_iter and status must not be NULL");
-  if (dtype == POGS_AMD_F64) solve_many_t<double>(ord, k, m, n, A, mem, device, f, g, rho, p, out);
-  else solve_many_t<float>(ord, k, m, n, A, mem, device, f, g, rho, p, out);
+  if (dtype == POGS_AMD_F64) {
+    ManyShapes<double> sh;
+    sh.set_uniform(k, m, n);
+    solve_many_t<double>(ord, sh, A, mem, device, f, g, rho, p, out);
+  } else {
+    ManyShapes<float> sh;
+    sh.set_uniform(k, m, n);
+    solve_many_t<float>(ord, sh, A, mem, device, f, g, rho, p, out);
+  }
 }
 
 void many_setup_check(int dtype, int ord, int k, size_t m, size_t n, const void *A, int mem, void *A_eq, void *d,

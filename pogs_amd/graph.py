@@ -484,6 +484,144 @@ def solve_many(A, fs, gs, rho=1.0, abs_tol=1e-4, rel_tol=1e-4, max_iter=2500, ve
             "status": status.astype(np.int64)}
 
 
+def _ragged_matrices(As, dtype, shapes, order, who):
+    """(k, ms, ns, pointer, mem, ord, dtype, device, keep-alive) of the matrices of a ragged call: ``As`` a sequence
+    of 2-D arrays / tensors, or (with ``shapes``) one packed 1-D array / tensor holding them back to back."""
+    if order not in ("C", "F"):
+        raise ValueError("%s: order must be 'C' or 'F', got %r" % (who, order))
+
+    def is_tensor(a):
+        return hasattr(a, "data_ptr") and hasattr(a, "is_cuda")
+
+    if shapes is not None:                                        # one packed buffer
+        shp = [tuple(int(v) for v in s) for s in shapes]
+        if not shp or any(len(s) != 2 or s[0] < 1 or s[1] < 1 for s in shp):
+            raise ValueError("%s: shapes must be k >= 1 pairs (m_j, n_j) of positive sizes" % who)
+        total = sum(m * n for m, n in shp)
+        ordc = Ordering.ROW_MAJ if order == "C" else Ordering.COL_MAJ
+        if is_tensor(As):
+            import torch
+
+            tdt = {torch.float32: np.float32, torch.float64: np.float64}.get(As.dtype)
+            if tdt is None:
+                raise ValueError("%s: A must be float32 or float64" % who)
+            dt = _resolve_dtype(tdt if dtype is None else dtype)
+            if dt != np.dtype(tdt):
+                raise ValueError("%s: a device tensor is read in place: its dtype must be the solve's dtype" % who)
+            if As.dim() != 1 or As.numel() != total or not As.is_contiguous():
+                raise ValueError("%s: a packed A must be one contiguous 1-D tensor of sum m_j n_j = %d elements"
+                                 % (who, total))
+            if not As.is_cuda:
+                return _ragged_matrices(As.numpy(), dt, shp, order, who)
+            _lib.check_device_pointer_interop()
+            return (len(shp), [s[0] for s in shp], [s[1] for s in shp], ctypes.c_void_p(As.data_ptr()), _lib.DEVICE,
+                    ordc, dt, As.device.index, As)
+        dt = _resolve_dtype(dtype)
+        arr = np.asarray(As)
+        if arr.ndim != 1 or arr.size != total:
+            raise ValueError("%s: a packed A must be one 1-D array of sum m_j n_j = %d elements" % (who, total))
+        arr = np.ascontiguousarray(arr, dtype=dt)
+        return len(shp), [s[0] for s in shp], [s[1] for s in shp], _ptr(arr), _lib.HOST, ordc, dt, None, arr
+
+    if is_tensor(As) or isinstance(As, np.ndarray) or not hasattr(As, "__len__"):
+        raise ValueError("%s: As must be a sequence of 2-D arrays (or one packed array with shapes=...)" % who)
+    mats = list(As)
+    if not mats:
+        raise ValueError("%s: As must hold k >= 1 matrices" % who)
+    if all(is_tensor(a) for a in mats) and all(a.is_cuda for a in mats):
+        import torch
+
+        if any(a.dim() != 2 for a in mats):
+            raise ValueError("%s: every member of As must be two-dimensional" % who)
+        if any(a.dtype != mats[0].dtype or a.device != mats[0].device for a in mats):
+            raise ValueError("%s: device tensors must share one dtype and one device" % who)
+        shp = [tuple(a.shape) for a in mats]
+        if any(m < 1 or n < 1 for m, n in shp):
+            raise ValueError("%s: every member of As must have at least one row and one column" % who)
+        packed = torch.cat([a.contiguous().reshape(-1) for a in mats])   # packed on the device, row-major
+        return _ragged_matrices(packed, dtype, shp, "C", who)
+    mats = [a.detach().cpu().numpy() if is_tensor(a) else np.asarray(a) for a in mats]
+    if any(a.ndim != 2 for a in mats):
+        raise ValueError("%s: every member of As must be two-dimensional, got %s"
+                         % (who, [a.ndim for a in mats if a.ndim != 2]))
+    if any(a.shape[0] < 1 or a.shape[1] < 1 for a in mats):
+        raise ValueError("%s: every member of As must have at least one row and one column" % who)
+    dt = _resolve_dtype(dtype)
+    # column-major when every member is Fortran-ordered; a member that is both (one row, one column) fits either
+    # order and does not decide
+    fortran = all(a.flags.f_contiguous for a in mats) and not all(a.flags.c_contiguous for a in mats)
+    flat = np.concatenate([np.asarray(a, dtype=dt).ravel(order="F" if fortran else "C") for a in mats])
+    return (len(mats), [a.shape[0] for a in mats], [a.shape[1] for a in mats], _ptr(flat), _lib.HOST,
+            Ordering.COL_MAJ if fortran else Ordering.ROW_MAJ, dt, None, flat)
+
+
+def _ragged_functions(who, fs, gs, ms, ns, dt, keep):
+    """The PogsAmdFn arrays of a ragged call after the count and length checks."""
+    k = len(ms)
+    fs, gs = list(fs), list(gs)
+    if len(fs) != k or len(gs) != k:
+        raise ValueError("%s: %d matrices, %d f and %d g function vectors" % (who, k, len(fs), len(gs)))
+    fa = (_lib.PogsAmdFn * k)()
+    ga = (_lib.PogsAmdFn * k)()
+    for j in range(k):
+        if len(fs[j]) != ms[j] or len(gs[j]) != ns[j]:
+            raise ValueError("%s: problem %d: f must have length %d and g length %d, got %d and %d"
+                             % (who, j, ms[j], ns[j], len(fs[j]), len(gs[j])))
+        fa[j] = _fn_struct(fs[j], ms[j], dt, keep)
+        ga[j] = _fn_struct(gs[j], ns[j], dt, keep)
+    return fa, ga
+
+
+def _ragged_split(flat, lens):
+    """The per-problem pieces (copies) of a packed output."""
+    ends = np.cumsum(lens)
+    return [flat[e - n:e].copy() for e, n in zip(ends, lens)]
+
+
+def solve_many_ragged(As, fs, gs, rho=1.0, abs_tol=1e-4, rel_tol=1e-4, max_iter=2500, verbose=0, adaptive_rho=True,
+                      gap_stop=True, dtype=None, device=-1, shapes=None, order="C"):
+    """`solve_many` for problems of unequal shapes: problem j has its own m_j x n_j matrix ``As[j]`` and functions
+    (fs[j]: length m_j, gs[j]: length n_j), all solved in one call (include/pogs_amd.h: PogsAmdSolveManyRaggedFn).
+    Problem j's results are the bytes `solve_many` returns for it alone.
+
+    ``As``: a sequence of 2-D arrays: host arrays (packed on the host; a list whose members are all Fortran-ordered
+    is passed column-major, one-row and one-column members fit either order), or torch tensors on one ROCm device
+    (packed on the device).  CPU tensors, and a list that mixes them with device tensors, are taken as host arrays.  With ``shapes`` (k pairs (m_j, n_j)),
+    ``As`` is instead ONE packed 1-D array or device tensor holding the matrices back to back, each in ``order``
+    ('C' or 'F'); a device tensor is read in place and never written.  ``rho``: one value or k values.
+    Returns a list of k dictionaries {'x': n_j, 'y': m_j, 'l': m_j, 'mu': n_j, 'optval', 'iterations', 'status'}."""
+    who = "solve_many_ragged"
+    k, ms, ns, aptr, mem, ordc, dt, tdev, keep_a = _ragged_matrices(As, dtype, shapes, order, who)
+    if np.ndim(rho) == 0:
+        rhos = np.full(k, float(rho))
+    else:
+        rhos = np.ascontiguousarray(rho, dtype=np.float64).ravel()
+        if len(rhos) != k:
+            raise ValueError("%s: %d problems and %d rho values" % (who, k, len(rhos)))
+    keep = []
+    fa, ga = _ragged_functions(who, fs, gs, ms, ns, dt, keep)
+    dev = tdev if (device == -1 and tdev is not None) else device
+    opt = _lib.PogsAmdOptions(device=dev, projector=_lib.PROJ_DIRECT)
+    M, N = int(sum(ms)), int(sum(ns))
+    x, mu = np.zeros(N, dt), np.zeros(N, dt)
+    y, l = np.zeros(M, dt), np.zeros(M, dt)
+    optval = np.zeros(k, np.float64)
+    final_iter = np.zeros(k, np.uint32)
+    status = np.zeros(k, np.int32)
+    marr = (ctypes.c_size_t * k)(*ms)
+    narr = (ctypes.c_size_t * k)(*ns)
+    code = _lib.F64 if dt == np.float64 else _lib.F32
+    st = lib.PogsAmdSolveManyRaggedFn(code, int(ordc), k, marr, narr, aptr, mem, ctypes.byref(opt), fa, ga, _ptr(rhos),
+                                      abs_tol, rel_tol, int(max_iter), int(verbose), int(adaptive_rho), int(gap_stop),
+                                      _ptr(x), _ptr(y), _ptr(l), _ptr(mu), _ptr(optval), _ptr(final_iter), _ptr(status))
+    del keep, keep_a
+    if st != 0:
+        raise RuntimeError("pogs_amd: ragged many-problem solve failed: " + _lib.last_error())
+    xs, mus, ys, ls = _ragged_split(x, ns), _ragged_split(mu, ns), _ragged_split(y, ms), _ragged_split(l, ms)
+    return [{"x": xs[j], "y": ys[j], "l": ls[j], "mu": mus[j], "optval": float(optval[j]),
+             "iterations": int(final_iter[j]), "status": int(status[j])} for j in range(k)]
+
+
 def solve_ridge(A, b, lambd, abs_tol=1e-4, rel_tol=1e-4, max_iter=2500, verbose=0, rho=1.0, dtype=None):
     """minimize 0.5 ||A x - b||^2 + 0.5 lambda ||x||^2   (reference: graph.py:436-476)"""
     m, n = _shape(A)
@@ -886,6 +1024,7 @@ class ManySolver:
     All k problems stay resident: a set that does not fit is refused, `solve_many` solves such a set in chunks."""
 
     _STARTS = {"cold": _lib.MANY_COLD, "warm": _lib.MANY_WARM_GIVEN, "last": _lib.MANY_WARM_LAST}
+    shapes = None        # a ragged handle (from_ragged): the k pairs (m_j, n_j)
 
     def __init__(self, A, dtype=None, device=-1):
         self._h = ctypes.c_void_p()
@@ -901,6 +1040,89 @@ class ManySolver:
             raise RuntimeError("pogs_amd: many-problem handle creation failed: " + _lib.last_error())
         _LIVE_SOLVERS.add(self)
 
+    @classmethod
+    def from_ragged(cls, As, dtype=None, device=-1, shapes=None, order="C"):
+        """A handle over problems of unequal shapes (include/pogs_amd.h: PogsAmdManyCreateRagged).  ``As``,
+        ``shapes`` and ``order`` as `solve_many_ragged` takes them.  `solve`, `info` and `close` work as on any
+        ManySolver; ``x0`` / ``l0`` are lists of k per-problem arrays, and so are the results' 'x', 'y', 'l', 'mu'.
+        ``m`` and ``n`` are the largest m_j and n_j, ``shapes`` the k pairs."""
+        k, ms, ns, aptr, mem, ordc, dt, tdev, keep_a = _ragged_matrices(As, dtype, shapes, order,
+                                                                         "ManySolver.from_ragged")
+        self = cls.__new__(cls)
+        self._h = ctypes.c_void_p()
+        self.k, self.m, self.n, self.dtype = k, max(ms), max(ns), np.dtype(dt)
+        self.shapes = list(zip(ms, ns))
+        dev = tdev if (device == -1 and tdev is not None) else device
+        opt = _lib.PogsAmdOptions(device=dev, projector=_lib.PROJ_DIRECT)
+        code = _lib.F64 if self.dtype == np.float64 else _lib.F32
+        marr = (ctypes.c_size_t * k)(*ms)
+        narr = (ctypes.c_size_t * k)(*ns)
+        st = lib.PogsAmdManyCreateRagged(ctypes.byref(self._h), code, int(ordc), k, marr, narr, aptr, mem,
+                                         ctypes.byref(opt))
+        del keep_a
+        if st != 0:
+            self._h = ctypes.c_void_p()
+            raise RuntimeError("pogs_amd: many-problem handle creation failed: " + _lib.last_error())
+        _LIVE_SOLVERS.add(self)
+        return self
+
+    def get_shapes(self):
+        """The k shapes (m_j, n_j) as the handle reports them (PogsAmdManyGetShapes); either kind of handle."""
+        if not self._h:
+            raise ValueError("ManySolver: the handle is closed")
+        marr = (ctypes.c_size_t * self.k)()
+        narr = (ctypes.c_size_t * self.k)()
+        if lib.PogsAmdManyGetShapes(self._h, marr, narr) != 0:
+            raise RuntimeError("pogs_amd: " + _lib.last_error())
+        return list(zip(list(marr), list(narr)))
+
+    def _solve_ragged(self, fs, gs, rho, start, x0, l0, abs_tol, rel_tol, max_iter, verbose, adaptive_rho, gap_stop):
+        k, dt = self.k, self.dtype
+        ms, ns = [s[0] for s in self.shapes], [s[1] for s in self.shapes]
+
+        def packed(v, lens, name):
+            v = list(v)
+            if len(v) != k:
+                raise ValueError("ManySolver: %s must be a list of %d per-problem arrays, got %d" % (name, k, len(v)))
+            parts = [np.asarray(a, dtype=dt) for a in v]
+            for j, a in enumerate(parts):
+                if a.shape != (lens[j],):
+                    raise ValueError("ManySolver: %s[%d] must have length %d, got shape %s"
+                                     % (name, j, lens[j], a.shape))
+            return np.ascontiguousarray(np.concatenate(parts))
+
+        if start == "warm":
+            if x0 is None or l0 is None:
+                raise ValueError("ManySolver: start='warm' needs both x0 and l0 (lists of k per-problem arrays)")
+            x0, l0 = packed(x0, ns, "x0"), packed(l0, ms, "l0")
+        elif x0 is not None or l0 is not None:
+            raise ValueError("ManySolver: x0 / l0 are read with start='warm' only")
+        rhos = None
+        if rho is not None:
+            rhos = np.full(k, float(rho)) if np.ndim(rho) == 0 else np.ascontiguousarray(rho, dtype=np.float64).ravel()
+            if len(rhos) != k:
+                raise ValueError("ManySolver: %d problems and %d rho values" % (k, len(rhos)))
+        keep = []
+        fa, ga = _ragged_functions("ManySolver", fs, gs, ms, ns, dt, keep)
+        M, N = int(sum(ms)), int(sum(ns))
+        x, mu = np.zeros(N, dt), np.zeros(N, dt)
+        y, l = np.zeros(M, dt), np.zeros(M, dt)
+        optval = np.zeros(k, np.float64)
+        final_iter = np.zeros(k, np.uint32)
+        status = np.zeros(k, np.int32)
+        rho_final = np.zeros(k, np.float64)
+        st = lib.PogsAmdManySolveFn(self._h, fa, ga, None if rhos is None else _ptr(rhos), self._STARTS[start],
+                                    None if x0 is None else _ptr(x0), None if l0 is None else _ptr(l0), abs_tol,
+                                    rel_tol, int(max_iter), int(verbose), int(adaptive_rho), int(gap_stop), _ptr(x),
+                                    _ptr(y), _ptr(l), _ptr(mu), _ptr(optval), _ptr(final_iter), _ptr(status),
+                                    _ptr(rho_final))
+        del keep
+        if st != 0:
+            raise RuntimeError("pogs_amd: many-problem solve failed: " + _lib.last_error())
+        return {"x": _ragged_split(x, ns), "y": _ragged_split(y, ms), "l": _ragged_split(l, ms),
+                "mu": _ragged_split(mu, ns), "optval": optval, "iterations": final_iter.astype(np.int64),
+                "status": status.astype(np.int64), "rho": rho_final}
+
     def solve(self, fs, gs, rho=None, start="cold", x0=None, l0=None, abs_tol=1e-4, rel_tol=1e-4, max_iter=2500,
               verbose=0, adaptive_rho=True, gap_stop=True):
         """Solve the k problems with (fs[j], gs[j]).  ``start``: "cold" (z = 0), "warm" (from ``x0``: k x n and
@@ -913,6 +1135,9 @@ class ManySolver:
             raise ValueError("ManySolver: the handle is closed")
         if start not in self._STARTS:
             raise ValueError("ManySolver: start must be 'cold', 'warm' or 'last', got %r" % (start,))
+        if self.shapes is not None:
+            return self._solve_ragged(fs, gs, rho, start, x0, l0, abs_tol, rel_tol, max_iter, verbose, adaptive_rho,
+                                      gap_stop)
         fs, gs = list(fs), list(gs)
         if len(fs) != k or len(gs) != k:
             raise ValueError("ManySolver: %d matrices, %d f and %d g function vectors" % (k, len(fs), len(gs)))
