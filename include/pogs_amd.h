@@ -216,7 +216,8 @@ int PogsAmdDistUniqueId(char *out);
  * Honoured for: dtype F64, m > n, projector DEFAULT or DIRECT, no dist, n <= 10240 (the row fits a one-pass shape of
  * the mixed plan: not windowed and no wider than the fp64 one-pass iteration reaches).  Refused before anything is
  * built -- POGS_ERROR, *out NULL, PogsAmdLastError names the reason: dtype F32, m <= n, either CGLS value, row shards,
- * a wider or windowed row, an unknown storage value.  PogsAmdCreateSparse refuses any non-zero storage. */
+ * a wider or windowed row, an unknown storage value.  PogsAmdCreateSparse refuses any non-zero storage (a sparse fp64
+ * handle over float non-zeros: PogsAmdCreateSparseMixed). */
 int PogsAmdCreateDense(PogsAmdSolver **out, int dtype, enum ORD ord, size_t m,
                        size_t n, const void *A, int mem,
                        const PogsAmdOptions *opt, const PogsAmdDist *dist);
@@ -236,6 +237,35 @@ int PogsAmdCreateSparse(PogsAmdSolver **out, int dtype, enum ORD ord, size_t m,
                         size_t n, size_t nnz, const void *data, const int *ptr,
                         const int *ind, int mem, const PogsAmdOptions *opt,
                         const PogsAmdDist *dist);
+
+/* Create a MIXED-STORAGE solver for a sparse matrix: an fp64 handle over float non-zeros (one GPU).  The arguments are
+ * those of PogsAmdCreateSparse with dtype POGS_AMD_F64 implied and no dist; opt->projector DEFAULT, CGLS or DIRECT as
+ * there.  PogsAmdCreateSparse itself keeps refusing a non-zero storage: the capability lives in this entry.
+ * The set-up runs as a plain fp64 handle's on the fp64 values -- structure, both CSR copies, both tiled copies,
+ * Sinkhorn-Knopp, D A E, the division by the norm -- so d and e are the plain handle's bytes.  Then every value of BOTH
+ * CSR copies is rounded to the nearest float and stored back as that double, val = (double)(float)val -- call the
+ * matrix A^ -- and EVERYTHING after that is defined on A^: the norm estimate, the sparse Gram matrix and factor of a
+ * DIRECT handle, every product, the residuals, the epilogue, PogsAmdGetEquil, PogsAmdMul, PogsAmdProject and the batch
+ * entries.  The handle solves, in fp64 arithmetic throughout, the graph-form problem of the matrix D^-1 A^ E^-1, which
+ * differs from the caller's A by at most 2^-24 relative per entry; it is not an approximate projector on the unrounded
+ * matrix.  The VALUES of the tiled copies are then written as floats (the fp64 arrays are released first, so the peak
+ * does not grow; local columns, row ids, tile table and plan are untouched) and every solo product -- the ADMM
+ * iteration, both CGLS loops, the norm estimate, warm start, PogsAmdMul, PogsAmdProject, PogsAmdSparseCgCheck, the
+ * direct projector's two products -- streams 4 instead of 8 bytes per value and widens it on use.  Both CSR copies hold
+ * bitwise-equal values, a float converts to double exactly and the order of every sum is fixed by the tile plan, so a
+ * product over the float values is BIT FOR BIT the fp64 product over A^.  The CSR copies stay fp64 with the rounded
+ * values: the plain CSR kernel (a copy that did not get tiled, POGS_AMD_SPMV=plain), the batched sparse kernels and the
+ * sparse Gram kernel read them, unchanged.  stats: stream_bytes counts a product on a float tiled copy with 4 instead
+ * of 8 in its nnz (s + 4) term; the vectors stay 8.  The handle holds 4 bytes less per stored element on each tiled copy.
+ * POGS_AMD_MIXED_PASS=0 in the environment, read at create, keeps the rounding but leaves the tiled values as doubles,
+ * the existing kernel over A^ (the A / B leg of a measurement; same bytes out).
+ * Refused before anything is built -- POGS_ERROR, *out NULL, PogsAmdLastError names the reason: a NULL argument (opt may
+ * be NULL), an unknown ord or mem, bad dimensions, projector CGLS_FUSED, DIRECT with min(m, n) >
+ * POGS_AMD_SPARSE_DIRECT_MAX, a storage field other than 0 or POGS_AMD_STORE_F32 (both mean float non-zeros here).
+ * Every entry that takes a sparse handle works on the result. */
+int PogsAmdCreateSparseMixed(PogsAmdSolver **out, enum ORD ord, size_t m, size_t n, size_t nnz,
+                             const double *data, const int *ptr, const int *ind, int mem,
+                             const PogsAmdOptions *opt);
 
 /* Cold-start solve (reference: PogsImplementation::Solve, src/cpu/pogs.cpp:91-581).
  * Coefficient and output pointers are HOST pointers of the solver's dtype
@@ -615,6 +645,15 @@ int PogsAmdSpmvCheck(int dtype, enum ORD ord, int nrows, int ncols, const int *p
                      int num_cu, int format, int force_rr_rows, int force_ncg, double scale, char trans, int sq,
                      double x_nrm2, double alpha, double beta, const void *x, size_t xlen, void *y, size_t ylen,
                      double *sumsq, int *info, int *t_ptr, int *t_ind, void *t_val);
+/* The same diagnostic for the product of a mixed-storage handle (PogsAmdCreateSparseMixed), fp64: the copies are built as
+ * PogsAmdSpmvCheck builds them for POGS_AMD_F64 and multiplied by `scale`; then every value of both CSR copies is rounded
+ * to the nearest float (kept as that double), the tiled values are written as FLOATS through the table of positions,
+ * and one product with the functor of the norm estimate runs on them (format 3: the plain CSR kernel on the rounded
+ * doubles).  There is no `sq`: the mixed kernel has no squared form.  Arguments, refusals and info as PogsAmdSpmvCheck. */
+int PogsAmdSpmvMixedCheck(enum ORD ord, int nrows, int ncols, const int *ptr, const int *ind, const double *val,
+                          int num_cu, int format, int force_rr_rows, int force_ncg, double scale, char trans,
+                          double x_nrm2, double alpha, double beta, const double *x, size_t xlen,
+                          double *y, size_t ylen, double *sumsq, int *info);
 /* Diagnostic of the sparse solver's projection: one run of its CGLS loop on given vectors, on a live sparse handle (one
  * GPU), by the member functions and launches an ADMM iteration uses, without the prox step.  HOST arrays of the handle's
  * type; n-sized: x0, x_warm, x_prev, x12, x, xtemp, p, sv; m-sized: y0, y_warm, y12, y_new, ytemp, r.  A is the handle's

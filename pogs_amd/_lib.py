@@ -113,6 +113,9 @@ lib.PogsAmdCreateDense.argtypes = [ctypes.POINTER(c_void_p), c_int, c_int, c_siz
 lib.PogsAmdCreateSparse.argtypes = [ctypes.POINTER(c_void_p), c_int, c_int, c_size_t, c_size_t, c_size_t, c_void_p,
                                     c_void_p, c_void_p, c_int, ctypes.POINTER(PogsAmdOptions),
                                     ctypes.POINTER(PogsAmdDist)]
+lib.PogsAmdCreateSparseMixed.argtypes = [ctypes.POINTER(c_void_p), c_int, c_size_t, c_size_t, c_size_t, c_void_p, c_void_p,
+                                         c_void_p, c_int, ctypes.POINTER(PogsAmdOptions)]
+lib.PogsAmdCreateSparseMixed.restype = c_int
 lib.PogsAmdSolve.argtypes = [c_void_p] + [c_void_p] * 12 + [c_double, c_double, c_double, c_uint, c_uint, c_int, c_int,
                                                             c_void_p, c_void_p, c_void_p, c_void_p,
                                                             ctypes.POINTER(c_double), ctypes.POINTER(c_uint)]
@@ -205,6 +208,10 @@ lib.PogsAmdCholCheck.argtypes = [c_int, c_int, c_void_p, c_size_t, c_void_p, c_v
 lib.PogsAmdSpmvCheck.argtypes = [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                  c_double, c_char, c_int, c_double, c_double, c_double, c_void_p, c_size_t, c_void_p,
                                  c_size_t, ctypes.POINTER(c_double), c_void_p, c_void_p, c_void_p, c_void_p]
+lib.PogsAmdSpmvMixedCheck.argtypes = [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                      c_double, c_char, c_double, c_double, c_double, c_void_p, c_size_t, c_void_p,
+                                      c_size_t, ctypes.POINTER(c_double), c_void_p]
+lib.PogsAmdSpmvMixedCheck.restype = c_int
 lib.PogsAmdSparseCgCheck.argtypes = [c_void_p] + [c_void_p] * 7 + [c_double, c_int, c_int, c_int, c_int] + [c_void_p] * 11
 lib.PogsAmdDenseCgCheck.argtypes = [c_void_p] + [c_void_p] * 4 + [c_double, c_int, c_int, c_int] + [c_void_p] * 9
 lib.PogsAmdGetFactor.argtypes = [c_void_p, c_void_p, c_void_p]
@@ -266,6 +273,7 @@ ABI_SYMBOLS = [
     "PogsAmdSpBatchSpmvCheck", "PogsAmdManySetupCheck", "PogsAmdGramCheck", "PogsAmdCholCheck",
     "PogsAmdSpmvCheck", "PogsAmdSparseCgCheck", "PogsAmdGetFactor", "PogsAmdSparseGramCheck", "PogsAmdTriMatvecCheck",
     "PogsAmdDensePassCheck", "PogsAmdDenseCgCheck", "PogsAmdVecCheck", "PogsAmdDensePassMixedCheck",
+    "PogsAmdCreateSparseMixed", "PogsAmdSpmvMixedCheck",
 ]
 
 
@@ -455,6 +463,34 @@ def spmv_check(ptr, ind, val, shape, x, y, trans="n", ord=ROW_MAJ, num_cu=0, for
     if t is None:
         return y, sumsq.value, infos
     return y, sumsq.value, infos, (t[0], t[1][:nnz], t[2][:nnz])
+
+
+def spmv_mixed_check(ptr, ind, val, shape, x, y, trans="n", ord=ROW_MAJ, num_cu=0, format=SPMV_AUTO, force_rr_rows=0,
+                     force_ncg=0, scale=1.0, x_nrm2=0.0, alpha=1.0, beta=0.0):
+    """(y, sumsq, (info_A, info_At)): the product of `spmv_check` as a mixed-storage sparse handle runs it (include/
+    pogs_amd.h: PogsAmdSpmvMixedCheck) -- float64 arrays; the values are multiplied by `scale`, rounded to float32 and
+    the tiled copies store them as float32.  No `sq`, no `transpose`.  Returns a new array; y itself is not changed."""
+    import numpy as np
+    ptr, ind = np.ascontiguousarray(ptr, dtype=np.int32), np.ascontiguousarray(ind, dtype=np.int32)
+    val, x = np.ascontiguousarray(val), np.ascontiguousarray(x)
+    y = np.array(y, order="C", copy=True)
+    if _dtype_code(val, x, y) != F64:
+        raise ValueError("the mixed product is float64: val, x and y must be float64 arrays")
+    nrows, ncols = int(shape[0]), int(shape[1])
+    r1 = nrows if ord == ROW_MAJ else ncols
+    if ptr.ndim != 1 or ptr.size != r1 + 1 or x.ndim != 1 or y.ndim != 1:
+        raise ValueError("ptr (rows of the given copy + 1), x and y vectors")
+    nnz = max(int(ptr[-1]), 0)
+    if ind.size < nnz or val.size < nnz:
+        raise ValueError("ind and val must hold ptr[-1] entries")
+    info = np.zeros(16, dtype=np.int32)
+    sumsq = c_double(0.0)
+    if lib.PogsAmdSpmvMixedCheck(ord, nrows, ncols, ptr.ctypes.data, ind.ctypes.data, val.ctypes.data, num_cu, format,
+                                 force_rr_rows, force_ncg, scale, trans.encode(), x_nrm2, alpha, beta, x.ctypes.data,
+                                 x.size, y.ctypes.data, y.size, ctypes.byref(sumsq), info.ctypes.data) != 0:
+        raise RuntimeError(last_error())
+    infos = tuple(dict(zip(SPMV_INFO, (int(v) for v in info[8 * c:8 * c + 8]))) for c in range(2))
+    return y, sumsq.value, infos
 
 
 def sparse_cg_check(handle, x0, y0, x_warm, y_warm, x_prev, x12, y12, tol, max_steps=500, ahead=1, ysync=False,

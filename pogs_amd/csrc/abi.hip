@@ -120,6 +120,8 @@ inline void dense_pass_mixed_check(const PogsAmdDensePassArgs *a) {
 SolverBase *make_sparse_solver(int dtype, int ord, size_t m, size_t n, size_t nnz, const void *data,
                                const int *ptr, const int *ind, int mem, const PogsAmdOptions *opt,
                                const PogsAmdDist *dist);
+SolverBase *make_sparse_solver_mixed(int ord, size_t m, size_t n, size_t nnz, const double *data, const int *ptr,
+                                     const int *ind, int mem, const PogsAmdOptions *opt);
 
 // gsl::rand (src/cpu/include/gsl/gsl_rand.h:8-16): a fresh
 // std::default_random_engine (libstdc++: minstd_rand0, x <- 16807 x mod 2^31-1,
@@ -380,6 +382,32 @@ int PogsAmdCreateSparse(PogsAmdSolver **out, int dtype, enum ORD ord, size_t m, 
     DeviceGuard guard(opt ? opt->device : -1);
     std::unique_ptr<PogsAmdSolver> h(new PogsAmdSolver);
     h->impl.reset(make_sparse_solver(dtype, ord, m, n, nnz, data, ptr, ind, mem, opt, dist));
+    *out = h.release();
+    return 0;
+  });
+}
+
+int PogsAmdCreateSparseMixed(PogsAmdSolver **out, enum ORD ord, size_t m, size_t n, size_t nnz, const double *data,
+                             const int *ptr, const int *ind, int mem, const PogsAmdOptions *opt) {
+  return guarded([&]() {
+    POGS_CHECK(out != nullptr, "null argument: out");
+    *out = nullptr;
+    // every refusal comes before anything is built (and before the first HIP call)
+    POGS_CHECK(data && ptr && ind, "null argument: data, ptr and ind are required");
+    POGS_CHECK(ord == ROW_MAJ || ord == COL_MAJ, "unknown ord (ROW_MAJ: CSR, COL_MAJ: CSC)");
+    POGS_CHECK(mem == POGS_AMD_HOST || mem == POGS_AMD_DEVICE, "unknown mem (POGS_AMD_HOST or POGS_AMD_DEVICE)");
+    POGS_CHECK(m > 0 && n > 0 && m < (1u << 31) && n < (1u << 31) && nnz < (1ull << 31), "bad dimensions");
+    if (opt) {
+      POGS_CHECK(opt->projector != POGS_AMD_PROJ_CGLS_FUSED,
+                 "POGS_AMD_PROJ_CGLS_FUSED is a dense projector (a sparse handle: POGS_AMD_PROJ_CGLS runs the device-resident loop)");
+      POGS_CHECK(opt->projector != POGS_AMD_PROJ_DIRECT || std::min(m, n) <= static_cast<size_t>(POGS_AMD_SPARSE_DIRECT_MAX),
+                 "the sparse direct projector needs min(m, n) <= POGS_AMD_SPARSE_DIRECT_MAX; use POGS_AMD_PROJ_CGLS");
+      POGS_CHECK(PogsAmdOptStorage(opt) == POGS_AMD_STORE_SAME || PogsAmdOptStorage(opt) == POGS_AMD_STORE_F32,
+                 "storage: unknown value (a mixed sparse handle takes 0 or POGS_AMD_STORE_F32; it stores float non-zeros either way)");
+    }
+    DeviceGuard guard(opt ? opt->device : -1);
+    std::unique_ptr<PogsAmdSolver> h(new PogsAmdSolver);
+    h->impl.reset(make_sparse_solver_mixed(static_cast<int>(ord), m, n, nnz, data, ptr, ind, mem, opt));
     *out = h.release();
     return 0;
   });
@@ -893,7 +921,20 @@ int PogsAmdSpmvCheck(int dtype, enum ORD ord, int nrows, int ncols, const int *p
   return guarded([&]() {
     const SpmvCheckArgs a{dtype, static_cast<int>(ord), nrows, ncols, ptr, ind, val, num_cu, format, force_rr_rows,
                           force_ncg, scale, trans, sq, x_nrm2, alpha, beta, x, xlen, y, ylen, sumsq, info, t_ptr, t_ind,
-                          t_val};
+                          t_val, 0};
+    spmv_check(a);
+    return 0;
+  });
+}
+
+int PogsAmdSpmvMixedCheck(enum ORD ord, int nrows, int ncols, const int *ptr, const int *ind, const double *val, int num_cu,
+                          int format, int force_rr_rows, int force_ncg, double scale, char trans, double x_nrm2,
+                          double alpha, double beta, const double *x, size_t xlen, double *y, size_t ylen, double *sumsq,
+                          int *info) {
+  return guarded([&]() {
+    const SpmvCheckArgs a{POGS_AMD_F64, static_cast<int>(ord), nrows, ncols, ptr, ind, val, num_cu, format, force_rr_rows,
+                          force_ncg, scale, trans, 0, x_nrm2, alpha, beta, x, xlen, y, ylen, sumsq, info, nullptr, nullptr,
+                          nullptr, 1};
     spmv_check(a);
     return 0;
   });

@@ -56,8 +56,16 @@
 //     more than their oldest batch, checked in the ISA) changed nothing: 1346 against 1340-1351 it/s -- the ring
 //     refills faster than a tile takes;
 // so what is left is bytes (8.4 per non-zero here).
+//
+// Mixed storage (PogsAmdCreateSparseMixed): the views, the batch and the kernel take a storage type S for the VALUES next
+// to the arithmetic type T.  S = T is everything above, instruction for instruction.  S = float under T = double reads
+// 4-byte values (one 16-byte load per batch instead of two) and widens them on use; the geometry is SellCfg<double>'s
+// and nothing else changes, so its sums are bit for bit the fp64 kernel's over the same (float-representable) values.
+// Measured: profiles/sparse_mixed_throughput.txt.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #include "common.h"
 #include "reduce.h"
@@ -86,9 +94,12 @@ constexpr unsigned short kSellNoRow = 0xFFFF;
 constexpr int kSellOffBits = 23;        // plan: stream offset of a row inside its tile (9 bits of stream above it)
 constexpr int kSellOff2Bits = 22;       // (two id slots) the offset; bit 22: the row's end is the SECOND one of its batch
 
-template <typename T>
+// S: the type the VALUES are stored in (T by default).  S = float under T = double is the mixed-storage copy of an fp64
+// handle (PogsAmdCreateSparseMixed): 4 bytes per value from memory, widened on use -- the geometry (SellCfg<T>), the x
+// slice, the row sums and every sum's order are those of T.
+template <typename T, typename S = T>
 struct SellView {
-  const T *val;
+  const S *val;
   const unsigned short *loc;    // column - first column of the tile's block
   const unsigned short *rid;    // tags: kSellNoRow, or (row - first row of the range) on the last element of a row;
                                 // two (below): per batch of a lane the rows of its first and second row end
@@ -108,9 +119,9 @@ struct SellView {
 // a lane are one 16-byte (fp32) vector, its local columns and row tags one 8-byte vector each, so a
 // wavefront fetches a batch with three fully coalesced wide loads; batch b of wavefront w of a tile
 // sits at element (first unit of the tile) * 64 + (b * 8 + w) * 256.
-template <typename T, bool TWO>
+template <typename T, bool TWO, typename S = T>
 struct SellBatch {
-  T v[kSellUB];
+  S v[kSellUB];   // (S = float under T = double: one 16-byte load instead of two)
   unsigned short c[kSellUB], r[TWO ? 1 : kSellUB];
   unsigned rr;   // (two id slots) both ids as loaded: first end's row in the low half, second's in the high half
 };
@@ -159,8 +170,8 @@ __device__ __forceinline__ int sell_uniform_load(const int *p) {
 
 // The row sums of one (row range, column group) into s_y[0 .. nr): the streaming body shared by the
 // SpMV kernels below.  s_x: BW elements of LDS, s_y: RR elements; ends with a barrier (s_y complete).
-template <typename T, bool SQ, bool TWO>
-__device__ __forceinline__ void sell_row_sums(const SellView<T> &A, const T *__restrict__ x, T xs, int rr, int cg, int nr,
+template <typename T, bool SQ, bool TWO, typename S = T>
+__device__ __forceinline__ void sell_row_sums(const SellView<T, S> &A, const T *__restrict__ x, T xs, int rr, int cg, int nr,
                                               T *s_x, T *s_y) {
   constexpr int BW = SellCfg<T>::BW;
   constexpr int UB = kSellUB, NB = kSellNB;
@@ -168,20 +179,22 @@ __device__ __forceinline__ void sell_row_sums(const SellView<T> &A, const T *__r
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
   for (int i = t; i < nr; i += kSellTpb) s_y[i] = 0;
 
-  const T *__restrict__ a_val = A.val;
+  static_assert(std::is_same<S, T>::value || (std::is_same<T, double>::value && std::is_same<S, float>::value && !SQ),
+                "a storage type of its own: float values under double arithmetic, never the squared form");
+  const S *__restrict__ a_val = A.val;
   const unsigned short *__restrict__ a_loc = A.loc;
   const unsigned short *__restrict__ a_rid = A.rid;
   const int *__restrict__ a_tu = A.tile_unit + static_cast<size_t>(rr) * A.ncb;   // this row range's tiles
   auto tu = [&](int cb) { return sell_uniform_load(a_tu + cb); };
 
-  auto fetch = [&](size_t e0, SellBatch<T, TWO> &B) {   // e0: first element of this lane's batch
+  auto fetch = [&](size_t e0, SellBatch<T, TWO, S> &B) {   // e0: first element of this lane's batch
 #ifndef POGS_SELL_VAL_NT
 #define POGS_SELL_VAL_NT 1
 #endif
 #ifndef POGS_SELL_LOC_NT
 #define POGS_SELL_LOC_NT 1
 #endif
-    sell_load<T, UB, POGS_SELL_VAL_NT != 0>(a_val + e0, B.v);
+    sell_load<S, UB, POGS_SELL_VAL_NT != 0>(a_val + e0, B.v);
     sell_load<unsigned short, UB, POGS_SELL_LOC_NT != 0>(a_loc + e0, B.c);
     // (measured at C4, round 5, alternating runs on one box: the values and the columns plain instead of non-temporal
     // cost 12 % / 7 % of the it/s; the id pair -- 1 byte per element -- is the other way round, plain 1283 against 1276 it/s.
@@ -201,7 +214,7 @@ __device__ __forceinline__ void sell_row_sums(const SellView<T> &A, const T *__r
 #define POGS_SELL_ABLATE 0
 #endif
   constexpr bool kNoLds = (POGS_SELL_ABLATE & 1) != 0, kNoIds = (POGS_SELL_ABLATE & 2) != 0;
-  auto consume = [&](const SellBatch<T, TWO> &B) {
+  auto consume = [&](const SellBatch<T, TWO, S> &B) {
     // (an ablation must not shrink the load stream: the id pair / tags stay loaded even where nothing reads them -- the
     // first form of these builds let the compiler drop that load, 1 of 7.35 bytes per element, and what it measured
     // was the bytes: profiles/NOTES_r06.md section 5)
@@ -226,7 +239,7 @@ __device__ __forceinline__ void sell_row_sums(const SellView<T> &A, const T *__r
     bool seen = false;   // (two id slots) a row has ended earlier in this batch: the next end is the second slot's
 #pragma unroll
     for (int j = 0; j < UB; ++j) {
-      const T v = B.v[j];
+      const T v = static_cast<T>(B.v[j]);   // (a stored float widens exactly)
       acc = sell_fma(SQ ? v * v : v, xg[j], acc);   // fused, written out: this unit is compiled with -ffp-contract=off
       if constexpr (kNoIds) {
         en[j] = false;
@@ -380,7 +393,7 @@ __device__ __forceinline__ void sell_row_sums(const SellView<T> &A, const T *__r
     first = f_b == 0 && f_cb < cb1;
     ++f_b;
   };
-  SellBatch<T, TWO> B[NB];
+  SellBatch<T, TWO, S> B[NB];
   bool first[NB];
   x_prefetch();
   if (tb > 0) {
@@ -419,8 +432,8 @@ __device__ __forceinline__ void sell_row_sums(const SellView<T> &A, const T *__r
 // column group's partial sums.  `guard` (may be null): a device word written by an EARLIER launch;
 // non-zero turns this launch into a no-op (the device-resident CG loop, cg_fused.h: the host
 // enqueues a loop's worth of launches without reading anything back).
-template <typename T, bool SQ, bool DIRECT, typename Op>
-__global__ void __launch_bounds__(kSellTpb) spmv_sell_kernel(SellView<T> A, const T *__restrict__ x,
+template <typename T, bool SQ, bool DIRECT, typename Op, typename S = T>
+__global__ void __launch_bounds__(kSellTpb) spmv_sell_kernel(SellView<T, S> A, const T *__restrict__ x,
                                                              const double *x_nrm2, Op op, T *__restrict__ part,
                                                              double *scalar_partials, const double *guard) {
   if (guard && *guard != 0.0) return;
@@ -442,8 +455,8 @@ __global__ void __launch_bounds__(kSellTpb) spmv_sell_kernel(SellView<T> A, cons
   T xs = 1;
   if (x_nrm2) xs = static_cast<T>(1.0 / sqrt(*x_nrm2));
   // (one uniform branch per launch: the two storage formats differ in what a batch fetches and how it names its rows)
-  if (A.two) sell_row_sums<T, SQ, true>(A, x, xs, rr, cg, nr, s_x, s_y);
-  else sell_row_sums<T, SQ, false>(A, x, xs, rr, cg, nr, s_x, s_y);
+  if (A.two) sell_row_sums<T, SQ, true, S>(A, x, xs, rr, cg, nr, s_x, s_y);
+  else sell_row_sums<T, SQ, false, S>(A, x, xs, rr, cg, nr, s_x, s_y);
   double sacc[NS];
 #pragma unroll
   for (int k = 0; k < NS; ++k) sacc[k] = 0.0;
@@ -876,10 +889,11 @@ __global__ void __launch_bounds__(256) sell_plan_kernel(const unsigned short *cn
 // (~2 steps at C4); for any other row a count over the row's prefix.  (One thread per row with a cursor per (row, tile)
 // in global memory -- 50 to 200 dependent read-modify-writes per thread -- took 8.7 ms per copy at C4.)
 // sloc == nullptr: values only (after a rescaling of the CSR copy).
-template <typename T>
+// S: the stored type of the tiled values (SellView), T by default.
+template <typename T, typename S = T>
 __global__ void __launch_bounds__(256) sell_fill_kernel(const T *val, const int *ind, const int *ptr, SellDims D,
                                                         const unsigned short *cnt, const unsigned *soff, const int *tile_unit,
-                                                        T *sval, unsigned short *sloc, unsigned short *srid, unsigned *dst_out,
+                                                        S *sval, unsigned short *sloc, unsigned short *srid, unsigned *dst_out,
                                                         int two) {
   // (rows whose column blocks are NOT in order -- an unsorted input: one running count per column block and wavefront in
   // LDS, the row taken 64 non-zeros at a time: an element's position is the count so far plus its rank among the lower
@@ -932,7 +946,7 @@ __global__ void __launch_bounds__(256) sell_fill_kernel(const T *val, const int 
       const size_t dst = static_cast<size_t>(u0) * 64 +
                          (static_cast<size_t>(k_el / kSellUB) * kSellWaves + (sidx >> 6)) * (64 * kSellUB) +
                          (sidx & 63) * kSellUB + (k_el % kSellUB);
-      sval[dst] = val[k];
+      sval[dst] = static_cast<S>(val[k]);
       if (dst_out) dst_out[k] = static_cast<unsigned>(dst);
       if (sloc) {
         const bool last = j + 1 == cnt[idx];
@@ -951,11 +965,11 @@ __global__ void __launch_bounds__(256) sell_fill_kernel(const T *val, const int 
 
 // sval[dst[k]] = val[k]: the values again (after a rescaling of the CSR copy), through the positions
 // sell_fill_kernel recorded -- coalesced reads, no per-(row, tile) bookkeeping
-template <typename T>
+template <typename T, typename S = T>
 __global__ void __launch_bounds__(256) sell_refill_kernel(const T *__restrict__ val, const unsigned *__restrict__ dst,
-                                                          size_t nnz, T *sval) {
+                                                          size_t nnz, S *sval) {
   for (size_t k = static_cast<size_t>(blockIdx.x) * 256 + threadIdx.x; k < nnz; k += static_cast<size_t>(gridDim.x) * 256)
-    sval[dst[k]] = val[k];
+    sval[dst[k]] = static_cast<S>(val[k]);
 }
 
 }  // namespace pogs_amd

@@ -59,8 +59,17 @@ template <typename T>
 class SparseSolver final : public SolverBase {
  public:
   SparseSolver(int ord, size_t m, size_t n, size_t nnz, const void *data, const int *ptr, const int *ind, int mem,
-               const PogsAmdOptions *opt, const PogsAmdDist *dist) {
+               const PogsAmdOptions *opt, const PogsAmdDist *dist, bool mixed = false) {
     const double t0 = wall_s();
+    // mixed storage (PogsAmdCreateSparseMixed; what it is honoured for is checked in abi.hip before anything is built):
+    // the equilibrated values are rounded to float and the tiled copies store them as floats.  POGS_AMD_MIXED_PASS=0
+    // keeps the rounding and leaves the tiled values as doubles (the A / B leg, the bit-for-bit yardstick).
+    mixed_ = mixed;
+    if (mixed_) {
+      POGS_CHECK((std::is_same<T, double>::value) && !(dist && dist->world >= 1), "mixed storage needs an fp64 handle on one GPU");
+      const char *mp = std::getenv("POGS_AMD_MIXED_PASS");
+      mixed_pass_ = !(mp && mp[0] == '0');
+    }
     // the direct projector (ProjectorDirect, projector_direct_dense.cpp, on a sparse A): refused before anything is built
     direct_ = opt && opt->projector == POGS_AMD_PROJ_DIRECT;
     if (direct_) {
@@ -453,7 +462,10 @@ class SparseSolver final : public SolverBase {
     const T normA = static_cast<T>(std::sqrt(S[kFro2])) /
                     static_cast<T>(std::sqrt(std::min(mg, nn)));
     op_->scal(static_cast<T>(1) / normA);
-    op_->finalize_values();
+    // mixed storage: from here on the matrix is the rounded one -- norm estimate, Gram matrix and factor, every product
+    // (d, e are those of the equilibration as it ran)
+    if (mixed_) op_->round_values();
+    op_->finalize_values(mixed_ && mixed_pass_);
     const T invs = static_cast<T>(1) / std::sqrt(normA);
     launch_scal<T>(d_.p, invs, m_, s);
     launch_scal<T>(e_.p, invs, n_, s);
@@ -981,7 +993,9 @@ class SparseSolver final : public SolverBase {
       ctx_.stats.stream_ms += ctx_.stream_timer.collect_ms(&cnt);
       ctx_.stats.stream_launches += cnt;
       // algorithmic bytes of one SpMV: nnz (s + 4) + 4 (rows + 1) + s (rows + cols)
-      const double per = static_cast<double>(nnz_) * (sizeof(T) + 4) + 4.0 * (0.5 * (m_ + n_) + 1) +
+      // (a mixed tiled copy streams 4-byte values; the products alternate between the copies, as the row term assumes)
+      const double vbytes = 0.5 * (op_->A().mixed ? 4.0 : sizeof(T)) + 0.5 * (op_->At().mixed ? 4.0 : sizeof(T));
+      const double per = static_cast<double>(nnz_) * (vbytes + 4) + 4.0 * (0.5 * (m_ + n_) + 1) +
                          static_cast<double>(sizeof(T)) * (m_ + n_);
       ctx_.stats.stream_bytes += static_cast<double>(cnt) * per;
     }
@@ -992,6 +1006,7 @@ class SparseSolver final : public SolverBase {
   int m_ = 0, n_ = 0;
   size_t nnz_ = 0;
   bool multi_ = false;
+  bool mixed_ = false, mixed_pass_ = false;   // mixed storage: values rounded to float; the tiled copies store floats
   std::optional<SparseOperator<T>> op_;   // A and A^T (built once ctx_ is initialised)
   DevBuf<T> tsum_;   // row shards: this rank's A^T partial sums before the all-reduce
   DevBuf<T> cg_u_;   // row shards, device-resident CG loop: A^T r over all ranks, kept by recurrence
@@ -1040,6 +1055,12 @@ SolverBase *make_sparse_solver(int dtype, int ord, size_t m, size_t n, size_t nn
   throw Error("unknown dtype");
 }
 
+// PogsAmdCreateSparseMixed: an fp64 handle over float non-zeros (include/pogs_amd.h)
+SolverBase *make_sparse_solver_mixed(int ord, size_t m, size_t n, size_t nnz, const double *data, const int *ptr,
+                                     const int *ind, int mem, const PogsAmdOptions *opt) {
+  return new SparseSolver<double>(ord, m, n, nnz, data, ptr, ind, mem, opt, nullptr, true);
+}
+
 namespace {
 // PogsAmdSpmvCheck: the copies as a solve builds them (SparseOperator, with the switches a solve reads from the
 // environment and the planner's two geometry choices as arguments), the second write of the values as equilibrate()
@@ -1067,7 +1088,8 @@ void spmv_check_t(const SpmvCheckArgs &a) {
     launch_fill<T>(sc.p, static_cast<T>(a.scale), mx, s);
     launch_fill<T>(one.p, static_cast<T>(1), mx, s);
     op.scale(sc.p, one.p, ctx.spart.p, ctx.spart.p + op.grid_cap());
-    op.finalize_values();
+    if (a.mixed) op.round_values();   // PogsAmdSpmvMixedCheck: rounded, then the tiled values as floats
+    op.finalize_values(a.mixed != 0);
     ctx.sync();   // sc / one are freed at scope exit
   }
   const DevCsr<T> &M = a.trans == 't' ? op.At() : op.A();
@@ -1170,6 +1192,7 @@ void tri_matvec_check(int dtype, int tri, int n, const void *M, size_t ldm, cons
 void spmv_check(const SpmvCheckArgs &a) {
   // every refusal comes before the first HIP call
   POGS_CHECK(a.dtype == POGS_AMD_F32 || a.dtype == POGS_AMD_F64, "unknown dtype");
+  POGS_CHECK(!a.mixed || (a.dtype == POGS_AMD_F64 && !a.sq), "the mixed product is fp64 and has no squared form");
   POGS_CHECK(a.ord == ROW_MAJ || a.ord == COL_MAJ, "unknown ord (ROW_MAJ: CSR, COL_MAJ: CSC)");
   POGS_CHECK(a.ptr && a.ind && a.val && a.x && a.y && a.sumsq && a.info, "null argument");
   POGS_CHECK(a.nrows >= 1 && a.ncols >= 1, "nrows and ncols must be >= 1");

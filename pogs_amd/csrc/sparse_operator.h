@@ -3,6 +3,8 @@
 // transposed on the device), their tiled lane-stream copies (sell.h: planned, filled, refilled once the values are
 // final), the product launchers on either copy and the per-XCD stamp diagnostic.  It works on a Ctx it is given and
 // knows nothing of ADMM, of functions or of row shards; PogsAmdSpmvCheck builds one without a solver.
+// Mixed storage (fp64 only): round_values() rounds both CSR copies to float-representable doubles, finalize_values(true)
+// then stores the tiled VALUES as floats and every product on a tiled copy runs the S = float kernel of sell.h.
 //
 // Included by sparse.hip only -- the anonymous namespace keeps every kernel in that translation unit.
 #include <algorithm>
@@ -187,6 +189,14 @@ __global__ void __launch_bounds__(256) sort_segments_kernel(const int *ptr, int 
   }
 }
 
+// val <- (double)(float) val, to nearest: the rounding of a mixed-storage handle (PogsAmdCreateSparseMixed).  Both CSR
+// copies hold bitwise-equal values when it runs (scale_csr_kernel: a commutative product), so they stay equal.
+__global__ void round_to_f32_kernel(double *val, size_t nnz) {
+  for (size_t k = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x; k < nnz;
+       k += static_cast<size_t>(gridDim.x) * blockDim.x)
+    val[k] = static_cast<double>(static_cast<float>(val[k]));
+}
+
 // ---------------------------------------------------------------------------
 template <typename T>
 struct DevCsr {
@@ -197,6 +207,8 @@ struct DevCsr {
   Csr<T> view() const { return Csr<T>{val.p, ind.p, ptr.p, blocks.p, nrows, nblocks}; }
   // tiled lane-stream copy (sell.h); sell_ready == false: not built, the plain kernel runs
   DevBuf<T> sval, part;
+  DevBuf<float> sval32;          // mixed storage (T = double): the tiled values as floats, INSTEAD of sval (finalize_values)
+  bool mixed = false;            // the tiled copy's values are sval32: every product runs the S = float kernel
   DevBuf<unsigned short> sloc, srid;
   DevBuf<int> tile_unit;
   DevBuf<unsigned short> scnt;   // build temporaries kept until the values are final (refill_sell)
@@ -213,6 +225,10 @@ struct DevCsr {
   SellView<T> sview() const {
     return SellView<T>{sval.p, sloc.p, srid.p, tile_unit.p, nrows, ncols, rr_rows, nrr, ncb, ncg, two,
                        stamps_on ? stamps.p : nullptr};
+  }
+  SellView<T, float> sview32() const {
+    return SellView<T, float>{sval32.p, sloc.p, srid.p, tile_unit.p, nrows, ncols, rr_rows, nrr, ncb, ncg, two,
+                              stamps_on ? stamps.p : nullptr};
   }
 };
 
@@ -286,10 +302,24 @@ class SparseOperator {
     launch_scal<T>(A_.val.p, alpha, nnz_, ctx_.stream);
     launch_scal<T>(At_.val.p, alpha, nnz_, ctx_.stream);
   }
-  // the CSR values are final: the tiled copies take them and the build temporaries go
-  void finalize_values() {
-    refill_sell(A_);
-    refill_sell(At_);
+  // Mixed storage: every value of both CSR copies rounded to the nearest float, kept as that double.  Called once the
+  // values are final, just before finalize_values(): everything after it is defined on the rounded matrix.
+  void round_values() {
+    if constexpr (std::is_same<T, double>::value) {
+      if (!nnz_) return;
+      const int g = static_cast<int>(std::min<size_t>((nnz_ + 255) / 256, static_cast<size_t>(ctx_.num_cu) * 32));
+      hipLaunchKernelGGL(round_to_f32_kernel, dim3(g), dim3(256), 0, ctx_.stream, A_.val.p, nnz_);
+      hipLaunchKernelGGL(round_to_f32_kernel, dim3(g), dim3(256), 0, ctx_.stream, At_.val.p, nnz_);
+    } else {
+      throw Error("mixed storage needs an fp64 operator");
+    }
+  }
+  // the CSR values are final: the tiled copies take them and the build temporaries go.  as_float (mixed storage, after
+  // round_values): the tiled values are written as floats -- the fp64 arrays are released first -- and every product
+  // on a tiled copy runs the S = float kernel from here on; loc, rid, tile_unit and the plan are untouched.
+  void finalize_values(bool as_float = false) {
+    refill_sell(A_, as_float);
+    refill_sell(At_, as_float);
   }
 
   // y_i = op(sum_k val * x[ind]) over the rows of M; scalar sums land in S[slot..slot+NS)
@@ -301,22 +331,11 @@ class SparseOperator {
     int grid;
     if (timed) ctx_.stream_timer.begin(s);
     if (M.sell_ready) {
-      constexpr size_t smem = sell_lds_bytes<T>();
-      const int g1 = M.nrr * M.ncg;
-      if (M.ncg == 1) {
-        static SmemGrants grants;
-        ensure_dynamic_smem(reinterpret_cast<const void *>(&spmv_sell_kernel<T, SQ, true, Op>), smem, grants);
-        hipLaunchKernelGGL((spmv_sell_kernel<T, SQ, true, Op>), dim3(g1), dim3(kSellTpb), smem, s, M.sview(), x,
-                           x_nrm2, op, static_cast<T *>(nullptr), ctx_.spart.p, static_cast<const double *>(nullptr));
-        grid = g1;
+      if (M.mixed) {
+        if constexpr (!SQ && std::is_same<T, double>::value) grid = launch_sell<false, float>(M, M.sview32(), x, x_nrm2, op);
+        else throw Error("the mixed tiled copy has no squared product");
       } else {
-        static SmemGrants grants;
-        ensure_dynamic_smem(reinterpret_cast<const void *>(&spmv_sell_kernel<T, SQ, false, Op>), smem, grants);
-        hipLaunchKernelGGL((spmv_sell_kernel<T, SQ, false, Op>), dim3(g1), dim3(kSellTpb), smem, s, M.sview(), x,
-                           x_nrm2, op, M.part.p, ctx_.spart.p, static_cast<const double *>(nullptr));
-        grid = std::max(1, std::min((M.nrows + 255) / 256, grid_cap_));
-        hipLaunchKernelGGL((reduce_parts_kernel<T, Op>), dim3(grid), dim3(256), 0, s, M.part.p, M.nrows, M.ncg, op,
-                           ctx_.spart.p);
+        grid = launch_sell<SQ, T>(M, M.sview(), x, x_nrm2, op);
       }
     } else {
       grid = std::max(1, std::min(M.nblocks, grid_cap_));
@@ -336,30 +355,11 @@ class SparseOperator {
   // go to `rec`; returns how many there are.  *ev: index of the stream-timer pair.
   template <typename Op>
   int spmv_cg(const DevCsr<T> &M, const T *x, const Op &op, double *rec, int run_if_done, size_t *ev) {
-    hipStream_t s = ctx_.stream;
-    constexpr size_t smem = sell_lds_bytes<T>();
-    const double *S = ctx_.S.p;
-    const double *guard = run_if_done == 0 ? S + kFcDone : nullptr;
-    const int g1 = M.nrr * M.ncg;
-    int nrec;
-    *ev = ctx_.stream_timer.begin(s);
-    if (M.ncg == 1) {
-      static SmemGrants grants;
-      ensure_dynamic_smem(reinterpret_cast<const void *>(&spmv_sell_kernel<T, false, true, Op>), smem, grants);
-      hipLaunchKernelGGL((spmv_sell_kernel<T, false, true, Op>), dim3(g1), dim3(kSellTpb), smem, s, M.sview(), x,
-                         static_cast<const double *>(nullptr), op, static_cast<T *>(nullptr), rec, guard);
-      nrec = g1;
-    } else {
-      static SmemGrants grants;
-      ensure_dynamic_smem(reinterpret_cast<const void *>(&spmv_sell_kernel<T, false, false, Op>), smem, grants);
-      hipLaunchKernelGGL((spmv_sell_kernel<T, false, false, Op>), dim3(g1), dim3(kSellTpb), smem, s, M.sview(), x,
-                         static_cast<const double *>(nullptr), op, M.part.p, rec, guard);
-      nrec = cgf_blocks(M.nrows);
-      hipLaunchKernelGGL((cgf_reduce_kernel<T, Op>), dim3(nrec), dim3(kCgfTpb), 0, s, M.part.p, M.nrows, M.ncg, op, rec, S,
-                         run_if_done);
+    if (M.mixed) {
+      if constexpr (std::is_same<T, double>::value) return launch_sell_cg<float>(M, M.sview32(), x, op, rec, run_if_done, ev);
+      else throw Error("mixed storage needs an fp64 operator");
     }
-    ctx_.stream_timer.end(s);
-    return nrec;
+    return launch_sell_cg<T>(M, M.sview(), x, op, rec, run_if_done, ev);
   }
 
   // the eight info words of PogsAmdSpmvCheck for copy c (0: A, 1: A^T)
@@ -390,6 +390,60 @@ class SparseOperator {
   }
 
  private:
+  // ---- the tiled kernel's launches, for either storage type S of the values (sell.h) -----------------------------
+  // the product proper (and, with column groups, the reduction that runs the row functor); returns the number of
+  // workgroups that left scalar partials in ctx_.spart
+  template <bool SQ, typename S, typename Op>
+  int launch_sell(const DevCsr<T> &M, const SellView<T, S> &V, const T *x, const double *x_nrm2, const Op &op) {
+    hipStream_t s = ctx_.stream;
+    constexpr size_t smem = sell_lds_bytes<T>();
+    const int g1 = M.nrr * M.ncg;
+    if (M.ncg == 1) {
+      static SmemGrants grants;
+      ensure_dynamic_smem(reinterpret_cast<const void *>(&spmv_sell_kernel<T, SQ, true, Op, S>), smem, grants);
+      hipLaunchKernelGGL((spmv_sell_kernel<T, SQ, true, Op, S>), dim3(g1), dim3(kSellTpb), smem, s, V, x, x_nrm2, op,
+                         static_cast<T *>(nullptr), ctx_.spart.p, static_cast<const double *>(nullptr));
+      return g1;
+    }
+    static SmemGrants grants;
+    ensure_dynamic_smem(reinterpret_cast<const void *>(&spmv_sell_kernel<T, SQ, false, Op, S>), smem, grants);
+    hipLaunchKernelGGL((spmv_sell_kernel<T, SQ, false, Op, S>), dim3(g1), dim3(kSellTpb), smem, s, V, x, x_nrm2, op,
+                       M.part.p, ctx_.spart.p, static_cast<const double *>(nullptr));
+    const int grid = std::max(1, std::min((M.nrows + 255) / 256, grid_cap_));
+    hipLaunchKernelGGL((reduce_parts_kernel<T, Op>), dim3(grid), dim3(256), 0, s, M.part.p, M.nrows, M.ncg, op,
+                       ctx_.spart.p);
+    return grid;
+  }
+  // the same for a product of the device-resident CG loop (spmv_cg)
+  template <typename S, typename Op>
+  int launch_sell_cg(const DevCsr<T> &M, const SellView<T, S> &V, const T *x, const Op &op, double *rec, int run_if_done,
+                     size_t *ev) {
+    hipStream_t s = ctx_.stream;
+    constexpr size_t smem = sell_lds_bytes<T>();
+    const double *S0 = ctx_.S.p;
+    const double *guard = run_if_done == 0 ? S0 + kFcDone : nullptr;
+    const int g1 = M.nrr * M.ncg;
+    int nrec;
+    *ev = ctx_.stream_timer.begin(s);
+    if (M.ncg == 1) {
+      static SmemGrants grants;
+      ensure_dynamic_smem(reinterpret_cast<const void *>(&spmv_sell_kernel<T, false, true, Op, S>), smem, grants);
+      hipLaunchKernelGGL((spmv_sell_kernel<T, false, true, Op, S>), dim3(g1), dim3(kSellTpb), smem, s, V, x,
+                         static_cast<const double *>(nullptr), op, static_cast<T *>(nullptr), rec, guard);
+      nrec = g1;
+    } else {
+      static SmemGrants grants;
+      ensure_dynamic_smem(reinterpret_cast<const void *>(&spmv_sell_kernel<T, false, false, Op, S>), smem, grants);
+      hipLaunchKernelGGL((spmv_sell_kernel<T, false, false, Op, S>), dim3(g1), dim3(kSellTpb), smem, s, V, x,
+                         static_cast<const double *>(nullptr), op, M.part.p, rec, guard);
+      nrec = cgf_blocks(M.nrows);
+      hipLaunchKernelGGL((cgf_reduce_kernel<T, Op>), dim3(nrec), dim3(kCgfTpb), 0, s, M.part.p, M.nrows, M.ncg, op, rec, S0,
+                         run_if_done);
+    }
+    ctx_.stream_timer.end(s);
+    return nrec;
+  }
+
   // ---- build ---------------------------------------------------------------
   void build_structure(int ord, const void *data, const int *ptr, const int *ind, int mem) {
     hipStream_t s = ctx_.stream;
@@ -649,8 +703,27 @@ class SparseOperator {
     ctx_.sync();
   }
   // the values are final (equilibrated): refill and drop the build temporaries
-  void refill_sell(DevCsr<T> &M) {
-    if (M.sell_ready && M.sdst.p) {
+  void refill_sell(DevCsr<T> &M, bool as_float = false) {
+    if (as_float && M.sell_ready) {
+      // mixed storage: float values in the same places.  The fp64 array goes first (nothing in flight reads it: the
+      // stream is waited for), so the copy's peak does not grow; the padding of the streams stays zero.
+      ctx_.sync();
+      M.sval.release();
+      M.sval32.alloc(M.sell_elems);
+      M.sval32.zero(ctx_.stream);
+      if (M.sdst.p) {
+        const int g = static_cast<int>(std::min<size_t>((M.nnz + 255) / 256, static_cast<size_t>(ctx_.num_cu) * 32));
+        hipLaunchKernelGGL((sell_refill_kernel<T, float>), dim3(std::max(1, g)), dim3(256), 0, ctx_.stream, M.val.p,
+                           M.sdst.p, M.nnz, M.sval32.p);
+      } else {   // (no position table: a copy of 2^32 stored elements or more) the plan is walked again
+        const int g = std::max(1, std::min((M.nrows + 3) / 4, ctx_.num_cu * 32));
+        hipLaunchKernelGGL((sell_fill_kernel<T, float>), dim3(g), dim3(256), 0, ctx_.stream, M.val.p, M.ind.p, M.ptr.p,
+                           M.sdims(), M.scnt.p, M.ssoff.p, M.tile_unit.p, M.sval32.p,
+                           static_cast<unsigned short *>(nullptr), M.srid.p, static_cast<unsigned *>(nullptr), M.two);
+      }
+      ctx_.sync();
+      M.mixed = true;
+    } else if (M.sell_ready && M.sdst.p) {
       const int g = static_cast<int>(std::min<size_t>((M.nnz + 255) / 256, static_cast<size_t>(ctx_.num_cu) * 32));
       hipLaunchKernelGGL(sell_refill_kernel<T>, dim3(std::max(1, g)), dim3(256), 0, ctx_.stream, M.val.p, M.sdst.p, M.nnz,
                          M.sval.p);

@@ -27,6 +27,7 @@ struct SpmvCheckArgs {
   int *info;
   int *t_ptr, *t_ind;
   void *t_val;
+  int mixed;   // PogsAmdSpmvMixedCheck (dtype F64, sq 0): the values rounded to float and the tiled copies' values stored as floats
 };
 
 void spmv_check(const SpmvCheckArgs &a);

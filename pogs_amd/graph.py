@@ -204,6 +204,24 @@ def _resolve_storage(storage, dtype):
     return code
 
 
+def _resolve_values(values, dtype):
+    """Solver(values=...): True for float32 non-zeros under a float64 sparse solver.  None, np.float64 or np.float32."""
+    if values is None:
+        return False
+    try:
+        vdt = np.dtype(values) if isinstance(values, (type, np.dtype, str)) else None
+    except TypeError:
+        vdt = None
+    # (compared through `is None` first: numpy reads None as float64)
+    if vdt is not None and vdt == np.dtype(np.float64) and dtype == np.dtype(np.float64):
+        return False
+    if vdt is None or vdt != np.dtype(np.float32):
+        raise ValueError("values must be None, np.float64 (on a float64 solver) or np.float32")
+    if dtype != np.dtype(np.float64):
+        raise ValueError("values=float32 needs dtype=float64 (a float32 solver already stores float32)")
+    return True
+
+
 def _ptr(a):
     return a.ctypes.data_as(ctypes.c_void_p)
 
@@ -704,12 +722,27 @@ class Solver:
     equilibrated matrix is rounded to float32 and the handle solves, in float64 arithmetic, the problem of that rounded
     matrix; ``solve`` and ``iterate`` read the float32 copy (1.5 x the matrix memory; PogsAmdCreateDense).  The
     attribute ``storage`` holds STORE_SAME or STORE_F32.
+    ``values``: None / np.float64: as ``dtype``.  np.float32 with ``dtype=np.float64`` on a SPARSE matrix (scipy, or the
+    device-CSR tuple; one GPU, projector DEFAULT / CGLS / DIRECT): mixed storage -- the equilibrated non-zeros are
+    rounded to float32 and the handle solves, in float64 arithmetic, the problem of that rounded matrix; every solo
+    product streams float32 values, bit for bit the float64 product over the rounded values, and the handle holds 4
+    bytes less per stored element on each tiled copy (PogsAmdCreateSparseMixed).  ``storage`` then reads STORE_F32.
+    ``storage=`` itself stays a dense option (a sparse matrix refuses it); the two keywords do not combine.
     """
 
     def __init__(self, A, dtype=None, shape=None, device_ptr=False, order=Ordering.ROW_MAJ, device=-1,
-                 profile=False, projector=_lib.PROJ_DEFAULT, dist=None, storage=None):
+                 profile=False, projector=_lib.PROJ_DEFAULT, dist=None, storage=None, values=None):
         self.dtype = _resolve_dtype(dtype)
         self.storage = _resolve_storage(storage, self.dtype)   # (ValueError before the library is called)
+        mixed_values = _resolve_values(values, self.dtype)   # (the same)
+        if mixed_values:
+            if storage is not None:
+                raise ValueError("values=float32 (sparse) and storage= (dense) do not combine: give one of them")
+            if dist is not None:
+                raise ValueError("values=float32 is single-GPU (row shards are not supported)")
+            if not ((device_ptr and isinstance(A, (tuple, list))) or ((not device_ptr) and HAS_SCIPY and sp.issparse(A))):
+                raise ValueError("values=float32 is the sparse option; a dense matrix takes storage=np.float32")
+            self.storage = STORE_F32
         self._h = ctypes.c_void_p()
         code = _lib.F64 if self.dtype == np.float64 else _lib.F32
         opt = _lib.PogsAmdOptions(device=device, projector=projector, profile=int(profile), storage=self.storage)
@@ -732,18 +765,28 @@ class Solver:
             self.sparse = True
             self.m, self.n = shape
             dptr, pptr, iptr, nnz = (int(v) for v in A)
-            st = lib.PogsAmdCreateSparse(ctypes.byref(self._h), code, int(Ordering.ROW_MAJ), self.m, self.n, nnz,
-                                         ctypes.c_void_p(dptr), ctypes.c_void_p(pptr), ctypes.c_void_p(iptr), _lib.DEVICE,
-                                         ctypes.byref(opt), ctypes.byref(dist_s) if dist_s is not None else None)
+            if mixed_values:
+                st = lib.PogsAmdCreateSparseMixed(ctypes.byref(self._h), int(Ordering.ROW_MAJ), self.m, self.n, nnz,
+                                                  ctypes.c_void_p(dptr), ctypes.c_void_p(pptr), ctypes.c_void_p(iptr),
+                                                  _lib.DEVICE, ctypes.byref(opt))
+            else:
+                st = lib.PogsAmdCreateSparse(ctypes.byref(self._h), code, int(Ordering.ROW_MAJ), self.m, self.n, nnz,
+                                             ctypes.c_void_p(dptr), ctypes.c_void_p(pptr), ctypes.c_void_p(iptr),
+                                             _lib.DEVICE, ctypes.byref(opt),
+                                             ctypes.byref(dist_s) if dist_s is not None else None)
         elif self.sparse:
             A_csr = sp.csr_matrix(A, dtype=self.dtype)
             self.m, self.n = A_csr.shape
             data = np.ascontiguousarray(A_csr.data, dtype=self.dtype)
             ptr = np.ascontiguousarray(A_csr.indptr, dtype=np.int32)
             ind = np.ascontiguousarray(A_csr.indices, dtype=np.int32)
-            st = lib.PogsAmdCreateSparse(ctypes.byref(self._h), code, int(Ordering.ROW_MAJ), self.m, self.n,
-                                         A_csr.nnz, _ptr(data), _ptr(ptr), _ptr(ind), _lib.HOST, ctypes.byref(opt),
-                                         ctypes.byref(dist_s) if dist_s is not None else None)
+            if mixed_values:
+                st = lib.PogsAmdCreateSparseMixed(ctypes.byref(self._h), int(Ordering.ROW_MAJ), self.m, self.n, A_csr.nnz,
+                                                  _ptr(data), _ptr(ptr), _ptr(ind), _lib.HOST, ctypes.byref(opt))
+            else:
+                st = lib.PogsAmdCreateSparse(ctypes.byref(self._h), code, int(Ordering.ROW_MAJ), self.m, self.n,
+                                             A_csr.nnz, _ptr(data), _ptr(ptr), _ptr(ind), _lib.HOST, ctypes.byref(opt),
+                                             ctypes.byref(dist_s) if dist_s is not None else None)
         else:
             if device_ptr:
                 self.m, self.n = shape
