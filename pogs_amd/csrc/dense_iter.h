@@ -1,16 +1,12 @@
-// DenseSolver: per-solve state and the ADMM iterations for m > n (PogsImplementation::Solve, src/cpu/pogs.cpp:91-581):
-// the two-pass iteration and the one-pass iteration with rho speculation; objective, epilogue.
+// DenseSolver: its hooks of SoloSolver<T> (solo_solver.h) and the ADMM iterations for m > n (PogsImplementation::Solve,
+// src/cpu/pogs.cpp:91-581): the two-pass iteration and the one-pass iteration with rho speculation.
 // Member definitions of the class template declared in dense_solver.h, which includes this file once, right after the
 // class, inside its namespaces (no include guard, no namespace of its own).
 
 // ---- per-solve -----------------------------------------------------------
 template <typename T, typename Tag>
 void DenseSolver<T, Tag>::load_problem(const FnHost &f, const FnHost &g, const SolveParams &p) {
-  hipStream_t s = ctx_.stream;
-  upload_fn<T>(f_, f, m_, s);
-  upload_fn<T>(g_, g, n_, s);
-  warn_negative_coeffs<T>(f, m_);   // prox_lib.h:62-69 (the clamp is in scale_objective_kernel)
-  warn_negative_coeffs<T>(g, n_);
+  load_functions(f, g);
   // the one-pass kernel evaluates prox_f inline: only for the cheap base functions
   bool all_cheap = true, all_logistic = true;
   if (tmode_) {   // transposed storage: it is prox_g that runs inside the pass
@@ -20,35 +16,21 @@ void DenseSolver<T, Tag>::load_problem(const FnHost &f, const FnHost &g, const S
     all_cheap = all_h(f, m_, [](int h) { return is_cheap_prox(h); });
     all_logistic = all_h(f, m_, [](int h) { return h == kLogistic; });
   }
-  pre_cheap_ = all_h(f, m_, [](int h) { return is_cheap_prox(h); }) && all_h(g, n_, [](int h) { return is_cheap_prox(h); });
   fused_now_ = fused_ok_ && (all_cheap || all_logistic);
   fused_logistic_ = fused_now_ && all_logistic && !all_cheap;
   tune_stream_plan<T>(planA_, fused_now_, fused_logistic_, tmode_);   // (stream.h: workgroups per CU, the prefetching form)
-  // scaled copies: h and b shared with the originals (pogs.cpp:608-617)
-  launch_scale_objective<T>(f_.view(), fs_.a.p, fs_.c.p, fs_.d.p, fs_.e.p, d_.p, m_, true, s);
-  launch_scale_objective<T>(g_.view(), gs_.a.p, gs_.c.p, gs_.d.p, gs_.e.p, e_.p, n_, false, s);
-  ctl_ = make_admm_control<T>(p, p.rho, ctx_.m_global, n_);
-  ctl_.say_rho = p.verbose > 3 && ctx_.dist.rank() == 0;
-  loaded_ = true;
-  ctx_.sync();  // the host coefficient arrays may be freed by the caller afterwards
+  arm_control(p);
 }
 
 template <typename T, typename Tag>
-void DenseSolver<T, Tag>::cold_start() {  // z = 0, zt = 0 (pogs.cpp:71-73,121-126)
-  hipStream_t s = ctx_.stream;
-  for (int i = 0; i < 2; ++i) { x_[i].zero(s); y_[i].zero(s); }
-  xt_.zero(s); yt_.zero(s); xtemp_.zero(s); ytemp_.zero(s);
-  cur_ = 0;
-  zt_scale_ = 1;
+void DenseSolver<T, Tag>::cold_start() {
+  reset_iterate();
   spec_valid_ = false;
   exact_mode_ = false;
   colparts_ = 0;
   proj_count_ = 0;
-  ctl_.reset();
 }
 
-// (x0, lambda0) -> (z, z~): z = [x0 / e | A (x0 / e)], z~ = -(1/rho) [-A^T (l0 / d) | l0 / d]
-// (pogs.cpp:144-156).  Consumed once.
 template <typename T, typename Tag>
 void DenseSolver<T, Tag>::apply_warm_start() {
   if (!warm_pending_) return;
@@ -83,17 +65,7 @@ bool DenseSolver<T, Tag>::iteration(unsigned verbose) {
   const int nw = cur_ ^ 1;
   const bool multi = multi_;
   // (1) prox + gap/tolerance sums + over-relaxation
-  AdmmPreArgs<T> pa;
-  pa.n_x = n_; pa.n_y = m_;
-  pa.g = gview(); pa.f = fview();
-  pa.x_cur = x_[cur_].p; pa.y_cur = y_[cur_].p;
-  pa.xt = xt_.p; pa.yt = yt_.p;
-  pa.zt_scale = zt_scale_;
-  pa.x12 = x12_.p; pa.y12 = y12_.p;
-  pa.xtemp = xtemp_.p; pa.ytemp = ytemp_.p;
-  pa.rho = ctl_.rho; pa.alpha = ctl_.alpha(); pa.cheap = pre_cheap_;
-  pa.partials = ctx_.spart.p;
-  pa.blocks_x = pre_blocks(n_);
+  const AdmmPreArgs<T> pa = pre_args();
   const double *S_fused = nullptr;
   if (cg_fused_) {
     // (1) + (2c) with the device-resident loop (dense_cg_fused.h): the prox launch starts the projection, the sums wait
@@ -195,12 +167,7 @@ bool DenseSolver<T, Tag>::iteration(unsigned verbose) {
   const bool stop = ctl_.check_stop(exact);
   log_iteration(verbose);
   if (stop) return true;
-  // (4) dual update already sits in xtemp/ytemp (ProjTailOp): swap roles.
-  std::swap(xt_, xtemp_);
-  std::swap(yt_, ytemp_);
-  cur_ = nw;
-  zt_scale_ = ctl_.adapt();
-  ++ctl_.k;
+  advance(nw);   // (4) dual update already sits in xtemp/ytemp (ProjTailOp): swap roles.
   return false;
 }
 
@@ -247,15 +214,8 @@ bool DenseSolver<T, Tag>::iteration_fused(unsigned verbose) {
     // (A') y half of the prox / over-relaxation, then (B) the column sums A^T yhat_k and
     // A^T (y12 + c yt - yprev) in a pass of their own -- a speculated iteration has both from
     // the previous pass (and its y-half sums on the host: spec_gap_ stands in for kGapY)
-    AdmmPreArgs<T> pa;
-    pa.n_x = 0; pa.n_y = m_;
-    pa.g = gview(); pa.f = fview();
-    pa.x_cur = x_[cur_].p; pa.y_cur = y_[cur_].p;
-    pa.xt = xt_.p; pa.yt = yt_.p;
-    pa.zt_scale = zt_scale_;
-    pa.x12 = x12_.p; pa.y12 = y12_.p;
-    pa.xtemp = xtemp_.p; pa.ytemp = ytemp_.p;
-    pa.rho = ctl_.rho; pa.alpha = ctl_.alpha(); pa.cheap = pre_cheap_;
+    AdmmPreArgs<T> pa = pre_args();
+    pa.n_x = 0;
     pa.partials = pre_part;
     pa.blocks_x = 0;
     launch_admm_pre<T>(pa, s);
@@ -404,10 +364,7 @@ bool DenseSolver<T, Tag>::iteration_fused(unsigned verbose) {
   const bool stop = ctl_.check_stop(exact);
   log_iteration(verbose);
   if (stop) return true;
-  std::swap(xt_, xtemp_);
-  std::swap(yt_, ytemp_);            // yt = ytilde_{k+1}
-  cur_ = nw;
-  zt_scale_ = ctl_.adapt();
+  advance(nw);                       // yt = ytilde_{k+1}
   if (!drop_spec && ctl_.rho == rho_pred_ && zt_scale_ == zs_pred_) {
     std::swap(ytemp_, ytemps_);      // ytemp = speculative yhat_{k+1}
     std::swap(y12_, y12s_);          // y12 = speculative y12_{k+1}
@@ -418,73 +375,12 @@ bool DenseSolver<T, Tag>::iteration_fused(unsigned verbose) {
     spec_valid_ = false;
     ctx_.stats.reserved[1] += 1;     // misses
   }
-  ++ctl_.k;
   return false;
 }
 
-// sum f(y12) + sum g(x12) at the current prox point (pogs.cpp:385, 473)
 template <typename T, typename Tag>
-double DenseSolver<T, Tag>::eval_objective() {
-  hipStream_t s = ctx_.stream;
-  const int by = vec_blocks(m_), bx = vec_blocks(n_);
-  const bool was_deferring = defer_sums_;
-  defer_sums_ = false;
-  launch_func_eval<T>(m_, fview(), y12_.p, ctx_.spart.p, s);
-  launch_func_eval<T>(n_, gview(), x12_.p, ctx_.spart.p + by, s);
-  SumJob j[2] = {{ctx_.spart.p, by, 1, ctx_.S.p + kFvalF}, {ctx_.spart.p + by, bx, 1, ctx_.S.p + kFvalG}};
-  launch_sum_jobs(j, 2, s);
-  if (multi_) ctx_.dist.allreduce(ctx_.S.p + kFvalF, 1, s);
-  const double *S = ctx_.fetch_scalars();
-  defer_sums_ = was_deferring;
-  return static_cast<double>(static_cast<T>(S[kFvalF]) + static_cast<T>(S[kFvalG]));
-}
-
-// the reference's per-iteration line (pogs.cpp:382-388); every rank evaluates (the objective
-// sum is a collective on row shards), rank 0 prints
-template <typename T, typename Tag>
-void DenseSolver<T, Tag>::log_iteration(unsigned verbose) {
-  if (!wants_iter_line(verbose, ctl_)) return;
-  const double obj = eval_objective();
-  if (ctx_.dist.rank() == 0) print_iter_line(ctl_, obj);
-}
-
-// optval, status, un-scaling, copy out (pogs.cpp:473-482, 510-518, 567-570).
-template <typename T, typename Tag>
-int DenseSolver<T, Tag>::epilogue(void *x, void *y, void *l, void *mu, double *optval) {
-  hipStream_t s = ctx_.stream;
-  const int by = vec_blocks(m_), bx = vec_blocks(n_);
-  launch_func_eval<T>(m_, fview(), y12_.p, ctx_.spart.p, s);
-  launch_func_eval<T>(n_, gview(), x12_.p, ctx_.spart.p + by, s);
-  SumJob j[2] = {{ctx_.spart.p, by, 1, ctx_.S.p + kFvalF}, {ctx_.spart.p + by, bx, 1, ctx_.S.p + kFvalG}};
-  launch_sum_jobs(j, 2, s);
-  if (multi_) ctx_.dist.allreduce(ctx_.S.p + kFvalF, 1, s);
-  UnscaleArgs<T> u;
-  u.n_x = n_; u.n_y = m_;
-  u.x12 = x12_.p; u.y12 = y12_.p; u.xt = xt_.p; u.yt = yt_.p;
-  u.xprev = x_[cur_].p; u.yprev = y_[cur_].p; u.d = d_.p; u.e = e_.p;
-  u.zt_scale = zt_scale_; u.rho = ctl_.rho;
-  u.x_out = xout_.p; u.y_out = yout_.p; u.l_out = lout_.p; u.mu_out = muout_.p;
-  launch_unscale<T>(u, s);
-  POGS_HIP_CHECK(hipMemcpyAsync(x, xout_.p, n_ * sizeof(T), hipMemcpyDeviceToHost, s));
-  POGS_HIP_CHECK(hipMemcpyAsync(y, yout_.p, m_ * sizeof(T), hipMemcpyDeviceToHost, s));
-  POGS_HIP_CHECK(hipMemcpyAsync(l, lout_.p, m_ * sizeof(T), hipMemcpyDeviceToHost, s));
-  if (mu) POGS_HIP_CHECK(hipMemcpyAsync(mu, muout_.p, n_ * sizeof(T), hipMemcpyDeviceToHost, s));
-  const double *S = ctx_.fetch_scalars();
-  *optval = static_cast<double>(static_cast<T>(S[kFvalF]) + static_cast<T>(S[kFvalG]));
-  // the polled sequence word says the kernels are done; the D2H copies into the caller's
-  // (pageable) buffers are only guaranteed complete after a synchronizing call
-  POGS_HIP_CHECK(hipStreamSynchronize(s));
-  return ctl_.status();
-}
-
-template <typename T, typename Tag>
-void DenseSolver<T, Tag>::collect_stream_timer() {
-  ctx_.stats.reserved[2] = static_cast<double>(ctx_.dist.collectives());   // all-reduce calls since creation
-  ctx_.stats.reserved[3] = static_cast<double>(ctx_.dist.comm_nranks());   // ranks as the communicator reports them
-  if (!ctx_.stream_timer.enabled()) return;
-  unsigned long long cnt = 0;
-  ctx_.stats.stream_ms += ctx_.stream_timer.collect_ms(&cnt);
-  ctx_.stats.stream_launches += cnt;
+void DenseSolver<T, Tag>::collect_timer() {
+  const unsigned long long cnt = collect_timer_head();
   // (a mixed launch reads the float copy: m n 4 bytes)
   const unsigned long long mixed = std::min(mixed_timed_, cnt);
   mixed_timed_ = 0;

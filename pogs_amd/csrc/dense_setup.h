@@ -70,16 +70,12 @@ void DenseSolver<T, Tag>::alloc_state() {
   hipStream_t s = ctx_.stream;
   const size_t np = n_pad_;
   const size_t mp = m_pad_;   // y-sized vectors are vector-loaded by the row kernel when T = A^T is stored
-  for (int i = 0; i < 2; ++i) { x_[i].alloc(np); y_[i].alloc(mp); x_[i].zero(s); y_[i].zero(s); }
-  xt_.alloc(np); yt_.alloc(mp); xtemp_.alloc(np); ytemp_.alloc(mp);
+  alloc_iterate(np, mp);
   const size_t kp = std::max<size_t>(np, k_pad_);
-  x12_.alloc(np); y12_.alloc(mp); rhs_.alloc(kp); tvec_.alloc(kp); tmpn_.alloc(kp);
-  xt_.zero(s); yt_.zero(s); xtemp_.zero(s); ytemp_.zero(s); x12_.zero(s); y12_.zero(s);
+  rhs_.alloc(kp); tvec_.alloc(kp); tmpn_.alloc(kp);
   rhs_.zero(s); tvec_.zero(s); tmpn_.zero(s);
-  d_.alloc(mp); d_.zero(s); e_.alloc(np); e_.zero(s);
+  d_.zero(s); e_.zero(s);
   if (tmode_) { uvec_.alloc(mp); uvec_.zero(s); }
-  xout_.alloc(np); yout_.alloc(m_); lout_.alloc(m_); muout_.alloc(np);
-  f_.alloc(m_); g_.alloc(n_); fs_.alloc(m_); gs_.alloc(n_);
   // (mixed storage: the mixed plan's launches may use more workgroups than planA_'s -- the partial-sum buffers take
   //  the larger of the two)
   const size_t gmax = std::max<size_t>(planA_.grid_max, mixed_store_ ? mixed_grid_max(planM_) : 0);

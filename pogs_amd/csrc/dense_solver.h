@@ -32,6 +32,7 @@
 #include "gram_phase.h"
 #include "ops.h"
 #include "reduce.h"
+#include "solo_solver.h"
 #include "stream.h"
 #include "stream_mixed.h"
 #include "vec_kernels.h"
@@ -94,7 +95,13 @@ __global__ void __launch_bounds__(256) scale_de_kernel(const T *src, T *dst, siz
 // Tag: the streaming shapes this instantiation carries (stream.h: OnePlan / WindowPlans /
 // AllPlans); dense_plan.hip builds one solver class per shape.
 template <typename T, typename Tag = AllPlans>
-class DenseSolver final : public SolverBase {
+class DenseSolver final : public SoloSolver<T> {
+  using B = SoloSolver<T>;
+  using B::begin_destroy, B::ctx_, B::m_, B::n_, B::multi_, B::d_, B::e_, B::nrmA_, B::x_, B::y_, B::xt_, B::yt_, B::xtemp_,
+      B::ytemp_, B::x12_, B::y12_, B::xout_, B::yout_, B::lout_, B::muout_, B::f_, B::g_, B::fs_, B::gs_, B::ctl_, B::loaded_,
+      B::cur_, B::zt_scale_, B::pre_cheap_, B::warm_pending_, B::warm_x_, B::warm_l_, B::fview, B::gview, B::alloc_iterate,
+      B::load_functions, B::arm_control, B::reset_iterate, B::pre_args, B::advance, B::collect_timer_head;
+
  public:
   ~DenseSolver() override { begin_destroy(ctx_); }
   DenseSolver(int ord, size_t m, size_t n, const void *A, int mem, const PogsAmdOptions *opt,
@@ -187,50 +194,6 @@ class DenseSolver final : public SolverBase {
     ctx_.stats.t_init_s = wall_s() - t0;
   }
 
-  int dtype() const override { return sizeof(T) == 4 ? POGS_AMD_F32 : POGS_AMD_F64; }
-  int device() const override { return ctx_.device; }
-  void on_entry() override { ctx_.on_entry(); }
-  void on_error() override { ctx_.on_error(); }
-  PogsAmdStats &stats() override { return ctx_.stats; }
-
-  int solve(const FnHost &f, const FnHost &g, const SolveParams &p, void *x, void *y, void *l, void *mu,
-            double *optval, unsigned *final_iter) override {
-    const double t0 = wall_s();
-    load_problem(f, g, p);
-    cold_start();
-    apply_warm_start();
-    ctx_.sync();
-    const double t1 = wall_s();
-    if (ctx_.dist.rank() == 0) print_banner(p.verbose);
-    while (!iteration(p.verbose)) {}
-    ctx_.sync();
-    const double t2 = wall_s();
-    const int status = epilogue(x, y, l, mu, optval);
-    *final_iter = ctl_.k;
-    PogsAmdStats &st = ctx_.stats;
-    st.t_loop_s = t2 - t1;
-    st.t_total_s = st.t_init_s + (wall_s() - t0);
-    st.iterations = ctl_.k + 1;
-    st.exact_iters = ctl_.exact_iters;
-    st.rho_updates = ctl_.rho_updates;
-    st.rho_final = ctl_.rho;
-    collect_stream_timer();
-    if (p.verbose > 0 && ctx_.dist.rank() == 0) {
-      print_summary(status, st.t_total_s, st.t_init_s, ctl_);
-      if (p.verbose > 3) print_timing_breakdown(st.t_loop_s, st.iterations);
-      std::printf("POGS-AMD dense/%s: status %d, iter %u, init %.3e s, loop %.3e s\n", cg_fused_ ? "cgls-fused" : use_cgls_ ? "cgls" : "direct",
-                  status, ctl_.k, st.t_init_s, st.t_loop_s);
-    }
-    return status;
-  }
-
-  void begin_run(const FnHost &f, const FnHost &g, const SolveParams &p) override {
-    load_problem(f, g, p);
-    cold_start();
-    apply_warm_start();
-    ctx_.sync();
-  }
-
   // Batched solves (the loop: batch_admm.h; its passes over the stored matrices: dense_batch.h): separate buffers; the
   // solo state, a pending warm start and the stats of the last solo solve stay as they are (except iterations, matvecs
   // and reserved[4..7]).  w: the members that start warm, cold by default.
@@ -239,33 +202,6 @@ class DenseSolver final : public SolverBase {
   void solve_batch_any(int k, const FnHost *f, const FnHost *g, const double *rho, const SolveParams &p,
                        const BatchOut &out, const BatchWarm &w) override {
     solve_batch(k, f, g, rho, p, out, w);
-  }
-
-  void set_warm_start(const void *x0, const void *l0) override {
-    warm_x_.assign(static_cast<const T *>(x0), static_cast<const T *>(x0) + n_);
-    warm_l_.assign(static_cast<const T *>(l0), static_cast<const T *>(l0) + m_);
-    warm_pending_ = true;
-  }
-
-  void iterate(unsigned iters, double *seconds, unsigned *solves) override {
-    POGS_CHECK(loaded_, "PogsAmdIterate before PogsAmdBeginRun / PogsAmdSolve: no problem is loaded");
-    unsigned done = 0;
-    ctx_.sync();
-    const double t0 = wall_s();
-    for (unsigned i = 0; i < iters; ++i) {
-      if (ctl_.finished) {
-        cold_start();
-        ++done;
-      }
-      iteration(0);
-    }
-    ctx_.sync();
-    const double t1 = wall_s();
-    if (seconds) *seconds = t1 - t0;
-    if (solves) *solves = done;
-    ctx_.stats.t_loop_s += t1 - t0;
-    ctx_.stats.iterations += iters;
-    collect_stream_timer();
   }
 
   void get_equil(void *A_eq, void *d, void *e, double *nrmA) override {
@@ -452,7 +388,7 @@ class DenseSolver final : public SolverBase {
       launch_reduce_cols<T, ColOp>(colpart, nparts, n_pad_, op, sp, s);
     } else {
       launch_reduce_cols<T, StoreColOp<T>>(colpart, nparts, n_pad_, StoreColOp<T>{1, 0, tmpn_.p, n_}, sp, s);
-      if (yslot_count > 0) ctx_.dist.allreduce2<T>(tmpn_.p, n_pad_, ctx_.S.p + yslot, yslot_count, s);
+      if (yslot_count > 0) ctx_.dist.allreduce2(tmpn_.p, n_pad_, ctx_.S.p + yslot, yslot_count, s);
       else ctx_.dist.allreduce(tmpn_.p, n_pad_, s);
       launch_reduce_cols<T, ColOp>(tmpn_.p, 1, n_pad_, op, sp, s);
     }
@@ -538,19 +474,16 @@ class DenseSolver final : public SolverBase {
   const double *prox_and_project_fused(const AdmmPreArgs<T> &pa0, int nw);
   void project_start_fused(double tol);
 
-  // ---- per-solve -----------------------------------------------------------
-  void load_problem(const FnHost &f, const FnHost &g, const SolveParams &p);
-  FnView<T> fview() const { return FnView<T>{f_.h.p, fs_.a.p, f_.b.p, fs_.c.p, fs_.d.p, fs_.e.p}; }
-  FnView<T> gview() const { return FnView<T>{g_.h.p, gs_.a.p, g_.b.p, gs_.c.p, gs_.d.p, gs_.e.p}; }
-
-  void cold_start();  // z = 0, zt = 0 (pogs.cpp:71-73,121-126)
-
-  // (x0, lambda0) -> (z, z~): z = [x0 / e | A (x0 / e)], z~ = -(1/rho) [-A^T (l0 / d) | l0 / d]
-  // (pogs.cpp:144-156).  Consumed once.
-  void apply_warm_start();
-
-  // One ADMM iteration (pogs.cpp:253-470).  Returns true when the solve stops.
-  bool iteration(unsigned verbose);
+  // ---- per-solve: the hooks of SoloSolver<T> -----------------------------------
+  void load_problem(const FnHost &f, const FnHost &g, const SolveParams &p) override;
+  void cold_start() override;
+  void apply_warm_start() override;
+  bool iteration(unsigned verbose) override;
+  void collect_timer() override;
+  void print_solver_line(int status) override {
+    std::printf("POGS-AMD dense/%s: status %d, iter %u, init %.3e s, loop %.3e s\n", cg_fused_ ? "cgls-fused" : use_cgls_ ? "cgls" : "direct",
+                status, ctl_.k, ctx_.stats.t_init_s, ctx_.stats.t_loop_s);
+  }
 
   // One ADMM iteration as ONE pass over A (two when the previous pass could not
   // speculate).  Same arithmetic as iteration(): the pass that forms y_{k+1} = A x_{k+1}
@@ -568,20 +501,16 @@ class DenseSolver final : public SolverBase {
   // (next right-hand side) and A x12_{k+1} (next exact primal residual).
   bool iteration_fused_wide(unsigned verbose);
 
-  // sum f(y12) + sum g(x12) at the current prox point (pogs.cpp:385, 473)
-  double eval_objective();
-  // the reference's per-iteration line (pogs.cpp:382-388); every rank evaluates (the objective
-  // sum is a collective on row shards), rank 0 prints
-  void log_iteration(unsigned verbose);
+  // the per-iteration line; inside the one-pass iteration the objective's launches see defer_sums_ off
+  void log_iteration(unsigned verbose) {
+    const bool was_deferring = defer_sums_;
+    defer_sums_ = false;
+    B::log_iteration(verbose);
+    defer_sums_ = was_deferring;
+  }
 
-  // optval, status, un-scaling, copy out (pogs.cpp:473-482, 510-518, 567-570).
-  int epilogue(void *x, void *y, void *l, void *mu, double *optval);
-
-  void collect_stream_timer();
-
-  Ctx ctx_;
-  int m_ = 0, n_ = 0, n_pad_ = 0, k_ = 0, k_pad_ = 0;
-  bool tall_ = true, multi_ = false, use_cgls_ = false;
+  int n_pad_ = 0, k_ = 0, k_pad_ = 0;
+  bool tall_ = true, use_cgls_ = false;
   double amax_ = 0;             // max |entry| of the equilibrated matrix (fp16 scaling of the Gram product)
   bool defer_sums_ = false;     // inside iteration_fused on one GPU: sums wait for the closing launch
   size_t sp_pre_off_ = 0, sp_tail_off_ = 0;   // regions of ctx_.spart (alloc_state)
@@ -607,30 +536,20 @@ class DenseSolver final : public SolverBase {
   MixedPlan planM_;
   DevBuf<float> A32_;
   size_t lda32_ = 0;
-  unsigned long long mixed_timed_ = 0;   // bracketed mixed launches since the last collect_stream_timer
+  unsigned long long mixed_timed_ = 0;   // bracketed mixed launches since the last collect_timer
   const T *A_src_ = nullptr;    // upload() .. equilibrate(): the caller's device buffer standing in for A_
-  bool pre_cheap_ = false;      // every f_i, g_j has a few-operation prox (admm_pre_kernel inlines it)
   T *Wp_ = nullptr, *Up_ = nullptr;   // views into fac_
-  DevBuf<T> A_, fac_, d_, e_, colpart_, colpart2_, y12s_, ytemps_;
+  DevBuf<T> A_, fac_, colpart_, colpart2_, y12s_, ytemps_;
   DevBuf<double> pack_;         // row shards, one-pass iteration: the packed all-reduce buffer
   bool fused_ok_ = false, fused_now_ = false, fused_logistic_ = false, spec_valid_ = false;
   // fp64, one GPU, m > n: the pass leaves the exact residuals out (one dot product, one accumulator, two
   // rows per step) until the approximate bounds first ask for them (iteration_fused)
   bool exact_mode_ = false;
   int colparts_ = 0;            // workgroups (= column partials) of the pass that filled colpart_ last
-  bool warm_pending_ = false;
-  std::vector<T> warm_x_, warm_l_;
   T rho_pred_ = 1, zs_pred_ = 1;
   int ysync_ = 16;                       // dense CGLS option: y = A x explicitly every ysync_-th projection (0: always)
   unsigned long long proj_count_ = 0;
-  DevBuf<T> x_[2], y_[2], xt_, yt_, xtemp_, ytemp_, x12_, y12_, rhs_, tvec_, tmpn_;
-  DevBuf<T> xout_, yout_, lout_, muout_;
-  FnBuf<T> f_, g_, fs_, gs_;
-  AdmmControl<T> ctl_;
-  bool loaded_ = false;   // load_problem has run: f, g and the control block are valid
-  int cur_ = 0;
-  T zt_scale_ = 1;
-  T nrmA_ = 0;
+  DevBuf<T> rhs_, tvec_, tmpn_;
 };
 
 // Member definitions, by seam (included HERE, inside the namespaces of the class): the one-time setup, the projector,

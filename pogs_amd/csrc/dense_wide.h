@@ -14,17 +14,8 @@ bool DenseSolver<T, Tag>::iteration_fused_wide(unsigned verbose) {
   const int nw = cur_ ^ 1;
   const int bx = pre_blocks(n_), by = pre_blocks(m_);
   // (A) prox / over-relaxation: y half always, x half unless already speculated
-  AdmmPreArgs<T> pa;
-  pa.n_x = spec_valid_ ? 0 : n_; pa.n_y = m_;
-  pa.g = gview(); pa.f = fview();
-  pa.x_cur = x_[cur_].p; pa.y_cur = y_[cur_].p;
-  pa.xt = xt_.p; pa.yt = yt_.p;
-  pa.zt_scale = zt_scale_;
-  pa.x12 = x12_.p; pa.y12 = y12_.p;
-  pa.xtemp = xtemp_.p; pa.ytemp = ytemp_.p;
-  pa.rho = ctl_.rho; pa.alpha = ctl_.alpha(); pa.cheap = pre_cheap_;
-  pa.partials = ctx_.spart.p;
-  pa.blocks_x = spec_valid_ ? 0 : bx;
+  AdmmPreArgs<T> pa = pre_args();
+  if (spec_valid_) pa.n_x = pa.blocks_x = 0;
   launch_admm_pre<T>(pa, s);
   if (spec_valid_) {
     SumJob j{ctx_.spart.p, by, 3, ctx_.S.p + kGapY};
@@ -86,10 +77,7 @@ bool DenseSolver<T, Tag>::iteration_fused_wide(unsigned verbose) {
   const bool stop = ctl_.check_stop(exact);
   log_iteration(verbose);
   if (stop) return true;
-  std::swap(xt_, xtemp_);            // xt = xtilde_{k+1}
-  std::swap(yt_, ytemp_);
-  cur_ = nw;
-  zt_scale_ = ctl_.adapt();
+  advance(nw);                       // xt = xtilde_{k+1}
   if (ctl_.rho == rho_pred_ && zt_scale_ == zs_pred_) {
     std::swap(xtemp_, xtemps_);      // xtemp = speculative xhat_{k+1}
     std::swap(x12_, x12s_);          // x12 = speculative x12_{k+1}
@@ -99,6 +87,5 @@ bool DenseSolver<T, Tag>::iteration_fused_wide(unsigned verbose) {
     spec_valid_ = false;
     ctx_.stats.reserved[1] += 1;
   }
-  ++ctl_.k;
   return false;
 }

@@ -20,7 +20,8 @@
 // One translation unit in four files: sparse_kernels.h (row functors, the plain SpMV and its companions),
 // sparse_operator.h (SparseOperator<T>: both copies, their build and their products), sparse_direct.h (the direct
 // projector's kernels: sparse Gram product, triangular mat-vec) and this one -- SparseSolver<T> (equilibration, norm
-// estimate, CGLS, the direct projector's factor and solves, the ADMM iteration, warm start, epilogue, stats),
+// estimate, CGLS, the direct projector's factor and solves, the ADMM iteration, warm start; the solve around them is
+// SoloSolver<T>, solo_solver.h),
 // PogsAmdSpmvCheck's spmv_check(), which runs one product on a SparseOperator of its own, without a solver, and the
 // same for the direct projector's kernels: sparse_gram_check() and tri_matvec_check().
 #include <algorithm>
@@ -39,6 +40,7 @@
 #include "gemm.h"
 #include "reduce.h"
 #include "sell.h"
+#include "solo_solver.h"
 #include "sparse_batch_kernels.h"
 #include "sparse_direct.h"
 #include "sparse_operator.h"
@@ -56,7 +58,14 @@ namespace {
 #define POGS_STR(x) POGS_STR2(x)
 
 template <typename T>
-class SparseSolver final : public SolverBase {
+class SparseSolver final : public SoloSolver<T> {
+  using B = SoloSolver<T>;
+  using B::begin_destroy, B::ctx_, B::m_, B::n_, B::multi_, B::d_, B::e_, B::nrmA_, B::x_, B::y_, B::xt_, B::yt_, B::xtemp_,
+      B::ytemp_, B::x12_, B::y12_, B::xout_, B::yout_, B::lout_, B::muout_, B::f_, B::g_, B::fs_, B::gs_, B::ctl_, B::loaded_,
+      B::cur_, B::zt_scale_, B::pre_cheap_, B::warm_pending_, B::warm_x_, B::warm_l_, B::fview, B::gview, B::alloc_iterate,
+      B::load_functions, B::arm_control, B::reset_iterate, B::pre_args, B::advance, B::reduce_y_scalars, B::log_iteration,
+      B::collect_timer_head;
+
  public:
   SparseSolver(int ord, size_t m, size_t n, size_t nnz, const void *data, const int *ptr, const int *ind, int mem,
                const PogsAmdOptions *opt, const PogsAmdDist *dist, bool mixed = false) {
@@ -106,50 +115,6 @@ class SparseSolver final : public SolverBase {
 
   ~SparseSolver() override { begin_destroy(ctx_); }
 
-  int dtype() const override { return sizeof(T) == 4 ? POGS_AMD_F32 : POGS_AMD_F64; }
-  int device() const override { return ctx_.device; }
-  void on_entry() override { ctx_.on_entry(); }
-  void on_error() override { ctx_.on_error(); }
-  PogsAmdStats &stats() override { return ctx_.stats; }
-
-  int solve(const FnHost &f, const FnHost &g, const SolveParams &p, void *x, void *y, void *l, void *mu,
-            double *optval, unsigned *final_iter) override {
-    const double t0 = wall_s();
-    load_problem(f, g, p);
-    cold_start();
-    apply_warm_start();
-    ctx_.sync();
-    const double t1 = wall_s();
-    if (ctx_.dist.rank() == 0) print_banner(p.verbose);
-    while (!iteration(p.verbose)) {}
-    ctx_.sync();
-    const double t2 = wall_s();
-    const int status = epilogue(x, y, l, mu, optval);
-    *final_iter = ctl_.k;
-    PogsAmdStats &st = ctx_.stats;
-    st.t_loop_s = t2 - t1;
-    st.t_total_s = st.t_init_s + (wall_s() - t0);
-    st.iterations = ctl_.k + 1;
-    st.exact_iters = ctl_.exact_iters;
-    st.rho_updates = ctl_.rho_updates;
-    st.rho_final = ctl_.rho;
-    collect_timer();
-    if (p.verbose > 0 && ctx_.dist.rank() == 0) {
-      print_summary(status, st.t_total_s, st.t_init_s, ctl_);
-      if (p.verbose > 3) print_timing_breakdown(st.t_loop_s, st.iterations);
-      std::printf("POGS-AMD sparse/%s: status %d, iter %u, init %.3e s, loop %.3e s, cg %llu, spmv %llu\n",
-                  direct_ ? "direct" : "cgls", status, ctl_.k, st.t_init_s, st.t_loop_s, st.cg_iters, st.matvecs);
-    }
-    return status;
-  }
-
-  void begin_run(const FnHost &f, const FnHost &g, const SolveParams &p) override {
-    load_problem(f, g, p);
-    cold_start();
-    apply_warm_start();
-    ctx_.sync();
-  }
-
   // k problems on the handle's matrix, every product with A / A^T shared (the loop: batch_admm.h; the
   // products and the batched CGLS: sparse_batch.h); w: the members that start warm, cold by default
   void solve_batch_sparse(int kb, const FnHost *f, const FnHost *g, const double *rho0, const SolveParams &p,
@@ -157,33 +122,6 @@ class SparseSolver final : public SolverBase {
   void solve_batch_any(int kb, const FnHost *f, const FnHost *g, const double *rho0, const SolveParams &p,
                        const BatchOut &out, const BatchWarm &w) override {
     solve_batch_sparse(kb, f, g, rho0, p, out, w);
-  }
-
-  void set_warm_start(const void *x0, const void *l0) override {
-    warm_x_.assign(static_cast<const T *>(x0), static_cast<const T *>(x0) + n_);
-    warm_l_.assign(static_cast<const T *>(l0), static_cast<const T *>(l0) + m_);
-    warm_pending_ = true;
-  }
-
-  void iterate(unsigned iters, double *seconds, unsigned *solves) override {
-    POGS_CHECK(loaded_, "PogsAmdIterate before PogsAmdBeginRun / PogsAmdSolve: no problem is loaded");
-    unsigned done = 0;
-    ctx_.sync();
-    const double t0 = wall_s();
-    for (unsigned i = 0; i < iters; ++i) {
-      if (ctl_.finished) {
-        cold_start();
-        ++done;
-      }
-      iteration(0);
-    }
-    ctx_.sync();
-    const double t1 = wall_s();
-    if (seconds) *seconds = t1 - t0;
-    if (solves) *solves = done;
-    ctx_.stats.t_loop_s += t1 - t0;
-    ctx_.stats.iterations += iters;
-    collect_timer();
   }
 
   void get_equil(void *A_eq, void *d, void *e, double *nrmA) override {
@@ -319,13 +257,8 @@ class SparseSolver final : public SolverBase {
  private:
   void alloc_state() {
     hipStream_t s = ctx_.stream;
-    for (int i = 0; i < 2; ++i) { x_[i].alloc(n_); y_[i].alloc(m_); x_[i].zero(s); y_[i].zero(s); }
-    xt_.alloc(n_); yt_.alloc(m_); xtemp_.alloc(n_); ytemp_.alloc(m_); x12_.alloc(n_); y12_.alloc(m_);
-    xt_.zero(s); yt_.zero(s); xtemp_.zero(s); ytemp_.zero(s); x12_.zero(s); y12_.zero(s);
-    d_.alloc(m_); e_.alloc(n_);
+    alloc_iterate(n_, m_);
     cg_p_.alloc(n_); cg_s_.alloc(n_); cg_q_.alloc(m_); cg_r_.alloc(m_); cg_b_.alloc(m_); u_.alloc(m_);
-    xout_.alloc(n_); yout_.alloc(m_); lout_.alloc(m_); muout_.alloc(n_);
-    f_.alloc(m_); g_.alloc(n_); fs_.alloc(m_); gs_.alloc(n_);
     cg_.alloc(kCgNumSlots);
     cg_.zero(s);
     if (multi_) { tsum_.alloc(n_); cg_u_.alloc(n_); cg_u_.zero(s); tsum_.zero(s); }
@@ -401,10 +334,6 @@ class SparseSolver final : public SolverBase {
       SumJob j{ctx_.spart.p, grid, Op::NS, scalar_out};
       launch_sum_jobs(&j, 1, s);
     }
-  }
-  // sums of a y-sized quantity: add the other ranks' rows
-  void reduce_y_scalars(double *slot, int count) {
-    if (multi_) ctx_.dist.allreduce(slot, count, ctx_.stream);
   }
 
   // MatrixSparse::Equil (matrix_sparse.cpp:158-242): Sinkhorn-Knopp on the squared
@@ -569,35 +498,18 @@ class SparseSolver final : public SolverBase {
     }
   }
 
-  // ---- per solve -----------------------------------------------------------
-  void load_problem(const FnHost &f, const FnHost &g, const SolveParams &p) {
-    hipStream_t s = ctx_.stream;
-    upload_fn<T>(f_, f, m_, s);
-    upload_fn<T>(g_, g, n_, s);
-    warn_negative_coeffs<T>(f, m_);   // prox_lib.h:62-69 (the clamp is in scale_objective_kernel)
-    warn_negative_coeffs<T>(g, n_);
-    pre_cheap_ = all_h(f, m_, [](int h) { return is_cheap_prox(h); }) && all_h(g, n_, [](int h) { return is_cheap_prox(h); });
-    launch_scale_objective<T>(f_.view(), fs_.a.p, fs_.c.p, fs_.d.p, fs_.e.p, d_.p, m_, true, s);
-    launch_scale_objective<T>(g_.view(), gs_.a.p, gs_.c.p, gs_.d.p, gs_.e.p, e_.p, n_, false, s);
+  // ---- per solve: the hooks of SoloSolver<T> ----------------------------------
+  void load_problem(const FnHost &f, const FnHost &g, const SolveParams &p) override {
+    load_functions(f, g);
     // coefficient arrays that hold one value throughout (a lasso: h, c, d, e of both halves) are not streamed by the
     // prox step: 16 of its 44 bytes per element
-    uni_f_ = probe_uniform<T>(fview(), m_, s);
-    uni_g_ = probe_uniform<T>(gview(), n_, s);
-    ctl_ = make_admm_control<T>(p, p.rho, ctx_.m_global, n_);
-    ctl_.say_rho = p.verbose > 3 && ctx_.dist.rank() == 0;
-    loaded_ = true;
-    ctx_.sync();
+    uni_f_ = probe_uniform<T>(fview(), m_, ctx_.stream);
+    uni_g_ = probe_uniform<T>(gview(), n_, ctx_.stream);
+    arm_control(p);
   }
-  FnView<T> fview() const { return FnView<T>{f_.h.p, fs_.a.p, f_.b.p, fs_.c.p, fs_.d.p, fs_.e.p}; }
-  FnView<T> gview() const { return FnView<T>{g_.h.p, gs_.a.p, g_.b.p, gs_.c.p, gs_.d.p, gs_.e.p}; }
 
-  void cold_start() {
-    hipStream_t s = ctx_.stream;
-    for (int i = 0; i < 2; ++i) { x_[i].zero(s); y_[i].zero(s); }
-    xt_.zero(s); yt_.zero(s); xtemp_.zero(s); ytemp_.zero(s);
-    cur_ = 0;
-    zt_scale_ = 1;
-    ctl_.reset();
+  void cold_start() override {
+    reset_iterate();
     proj_count_ = 0;
     cg_pred_ = 1;
   }
@@ -692,8 +604,7 @@ class SparseSolver final : public SolverBase {
     launch_axpby<T>(n_, static_cast<T>(1), x0, static_cast<T>(1), x, s);
   }
 
-  // (x0, lambda0) -> (z, z~)   (pogs.cpp:144-156), see dense_solver.h
-  void apply_warm_start() {
+  void apply_warm_start() override {
     if (!warm_pending_) return;
     warm_pending_ = false;
     hipStream_t s = ctx_.stream;
@@ -867,21 +778,12 @@ class SparseSolver final : public SolverBase {
     return Sh;
   }
 
-  bool iteration(unsigned verbose) {
+  bool iteration(unsigned verbose) override {
     hipStream_t s = ctx_.stream;
     const int nw = cur_ ^ 1;
-    AdmmPreArgs<T> pa;
-    pa.n_x = n_; pa.n_y = m_;
-    pa.g = gview(); pa.f = fview();
-    pa.x_cur = x_[cur_].p; pa.y_cur = y_[cur_].p;
-    pa.xt = xt_.p; pa.yt = yt_.p;
-    pa.zt_scale = zt_scale_;
-    pa.x12 = x12_.p; pa.y12 = y12_.p;
-    pa.xtemp = xtemp_.p; pa.ytemp = ytemp_.p;
-    pa.rho = ctl_.rho; pa.alpha = ctl_.alpha(); pa.cheap = pre_cheap_;
+    AdmmPreArgs<T> pa = pre_args();
     pa.uf = uni_f_; pa.ug = uni_g_;
     pa.partials = ctx_.spart.p + sp_pre_off_;
-    pa.blocks_x = pre_blocks(n_);
     const double *S;
     if (fused_cg_) {
       S = prox_and_project_fused(pa, nw);
@@ -931,67 +833,15 @@ class SparseSolver final : public SolverBase {
       exact = true;
     }
     const bool stop = ctl_.check_stop(exact);
-    if (wants_iter_line(verbose, ctl_)) {
-      const double obj = eval_objective();
-      if (ctx_.dist.rank() == 0) print_iter_line(ctl_, obj);
-    }
+    log_iteration(verbose);
     if (stop) return true;
-    std::swap(xt_, xtemp_);
-    std::swap(yt_, ytemp_);
-    cur_ = nw;
-    zt_scale_ = ctl_.adapt();
-    ++ctl_.k;
+    advance(nw);
     return false;
   }
 
-  // sum f(y12) + sum g(x12) at the current prox point (pogs.cpp:385, 473)
-  double eval_objective() {
-    hipStream_t s = ctx_.stream;
-    const int by = vec_blocks(m_), bx = vec_blocks(n_);
-    launch_func_eval<T>(m_, fview(), y12_.p, ctx_.spart.p, s);
-    launch_func_eval<T>(n_, gview(), x12_.p, ctx_.spart.p + by, s);
-    SumJob j[2] = {{ctx_.spart.p, by, 1, ctx_.S.p + kFvalF}, {ctx_.spart.p + by, bx, 1, ctx_.S.p + kFvalG}};
-    launch_sum_jobs(j, 2, s);
-    reduce_y_scalars(ctx_.S.p + kFvalF, 1);
-    const double *S = ctx_.fetch_scalars();
-    return static_cast<double>(static_cast<T>(S[kFvalF]) + static_cast<T>(S[kFvalG]));
-  }
-
-  int epilogue(void *x, void *y, void *l, void *mu, double *optval) {
-    hipStream_t s = ctx_.stream;
-    const int by = vec_blocks(m_), bx = vec_blocks(n_);
-    launch_func_eval<T>(m_, fview(), y12_.p, ctx_.spart.p, s);
-    launch_func_eval<T>(n_, gview(), x12_.p, ctx_.spart.p + by, s);
-    SumJob j[2] = {{ctx_.spart.p, by, 1, ctx_.S.p + kFvalF}, {ctx_.spart.p + by, bx, 1, ctx_.S.p + kFvalG}};
-    launch_sum_jobs(j, 2, s);
-    reduce_y_scalars(ctx_.S.p + kFvalF, 1);
-    UnscaleArgs<T> u;
-    u.n_x = n_; u.n_y = m_;
-    u.x12 = x12_.p; u.y12 = y12_.p; u.xt = xt_.p; u.yt = yt_.p;
-    u.xprev = x_[cur_].p; u.yprev = y_[cur_].p; u.d = d_.p; u.e = e_.p;
-    u.zt_scale = zt_scale_; u.rho = ctl_.rho;
-    u.x_out = xout_.p; u.y_out = yout_.p; u.l_out = lout_.p; u.mu_out = muout_.p;
-    launch_unscale<T>(u, s);
-    POGS_HIP_CHECK(hipMemcpyAsync(x, xout_.p, n_ * sizeof(T), hipMemcpyDeviceToHost, s));
-    POGS_HIP_CHECK(hipMemcpyAsync(y, yout_.p, m_ * sizeof(T), hipMemcpyDeviceToHost, s));
-    POGS_HIP_CHECK(hipMemcpyAsync(l, lout_.p, m_ * sizeof(T), hipMemcpyDeviceToHost, s));
-    if (mu) POGS_HIP_CHECK(hipMemcpyAsync(mu, muout_.p, n_ * sizeof(T), hipMemcpyDeviceToHost, s));
-    const double *S = ctx_.fetch_scalars();
-    *optval = static_cast<double>(static_cast<T>(S[kFvalF]) + static_cast<T>(S[kFvalG]));
-    // the polled sequence word says the kernels are done; the D2H copies into the caller's
-    // (pageable) buffers are only guaranteed complete after a synchronizing call
-    POGS_HIP_CHECK(hipStreamSynchronize(s));
-    return ctl_.status();
-  }
-
-  void collect_timer() {
-    ctx_.stats.reserved[2] = static_cast<double>(ctx_.dist.collectives());   // all-reduce calls since creation
-    ctx_.stats.reserved[3] = static_cast<double>(ctx_.dist.comm_nranks());   // ranks as the communicator reports them
+  void collect_timer() override {
     ctx_.stats.matvecs += timed_spmvs_;
-    if (ctx_.stream_timer.enabled()) {
-      unsigned long long cnt = 0;
-      ctx_.stats.stream_ms += ctx_.stream_timer.collect_ms(&cnt);
-      ctx_.stats.stream_launches += cnt;
+    if (const unsigned long long cnt = collect_timer_head()) {
       // algorithmic bytes of one SpMV: nnz (s + 4) + 4 (rows + 1) + s (rows + cols)
       // (a mixed tiled copy streams 4-byte values; the products alternate between the copies, as the row term assumes)
       const double vbytes = 0.5 * (op_->A().mixed ? 4.0 : sizeof(T)) + 0.5 * (op_->At().mixed ? 4.0 : sizeof(T));
@@ -1002,10 +852,13 @@ class SparseSolver final : public SolverBase {
     timed_spmvs_ = 0;
   }
 
-  Ctx ctx_;
-  int m_ = 0, n_ = 0;
+  void print_solver_line(int status) override {
+    const PogsAmdStats &st = ctx_.stats;
+    std::printf("POGS-AMD sparse/%s: status %d, iter %u, init %.3e s, loop %.3e s, cg %llu, spmv %llu\n",
+                direct_ ? "direct" : "cgls", status, ctl_.k, st.t_init_s, st.t_loop_s, st.cg_iters, st.matvecs);
+  }
+
   size_t nnz_ = 0;
-  bool multi_ = false;
   bool mixed_ = false, mixed_pass_ = false;   // mixed storage: values rounded to float; the tiled copies store floats
   std::optional<SparseOperator<T>> op_;   // A and A^T (built once ctx_ is initialised)
   DevBuf<T> tsum_;   // row shards: this rank's A^T partial sums before the all-reduce
@@ -1013,12 +866,7 @@ class SparseSolver final : public SolverBase {
   size_t sp_cgx_off_ = 0, sp_cgp_off_ = 0, sp_pre_off_ = 0;   // regions of ctx_.spart (alloc_state)
   unsigned long long timed_spmvs_ = 0;
   std::vector<size_t> fused_events_;
-  bool warm_pending_ = false;
-  std::vector<T> warm_x_, warm_l_;
-  DevBuf<T> d_, e_;
-  DevBuf<T> x_[2], y_[2], xt_, yt_, xtemp_, ytemp_, x12_, y12_;
   DevBuf<T> cg_p_, cg_s_, cg_q_, cg_r_, cg_b_, u_;
-  DevBuf<T> xout_, yout_, lout_, muout_;
   DevBuf<double> cg_;
   // direct projector (POGS_AMD_PROJ_DIRECT; factor_direct)
   bool direct_ = false, tall_ = true;
@@ -1034,14 +882,7 @@ class SparseSolver final : public SolverBase {
   size_t cg_rec_cap_ = 0;
   int ysync_ = 16;               // y = A x explicitly every ysync_-th iteration (0: always), else by recurrence
   unsigned long long proj_count_ = 0;
-  bool pre_cheap_ = false;       // every f_i, g_j has a few-operation prox (admm_pre_kernel inlines it)
   FnUniform<T> uni_f_, uni_g_;   // coefficient arrays of f / g that hold one value throughout (load_problem)
-  FnBuf<T> f_, g_, fs_, gs_;
-  AdmmControl<T> ctl_;
-  bool loaded_ = false;   // load_problem has run: f, g and the control block are valid
-  int cur_ = 0;
-  T zt_scale_ = 1;
-  T nrmA_ = 0;
 };
 
 #include "sparse_batch.h"

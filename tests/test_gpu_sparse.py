@@ -527,6 +527,29 @@ def test_sparse_warm_start_matches_oracle():
     _check(r3, cold, 1e-6, 2)
 
 
+def test_sparse_iterate_matches_solve_trajectory():
+    """bench stepping on the CSR + CGLS path (the device-resident loop): begin_run + iterate(k) walks the same
+    trajectory as solve(), and the second round restarts from the cold start."""
+    pogs = _pogs()
+    from pogs_amd import synth
+
+    A, b, _ = synth.csr_lasso(3000, 800, 20, seed=8, dtype=np.float64)
+    f, g = pogs.graph.lasso_functions(b, 0.2, 800)
+    with pogs.Solver(A, dtype=np.float64, profile=True) as s:
+        r = s.solve(f, g)
+        n_it = r["iterations"] + 1
+        s.reset_stats()
+        s.begin_run(f, g)
+        sec, solves = s.iterate(n_it)
+        assert solves == 0
+        sec, solves = s.iterate(n_it)
+        assert solves == 1
+        st = s.stats()
+        assert st["iterations"] == 2 * n_it
+        assert st["stream_launches"] > 0
+        assert st["stream_ms"] > 0
+
+
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
 def test_column_blocked_spmv_several_blocks(dtype):
     """Shapes past one LDS column block (28672 fp32 / 10240 fp64 columns) in both directions:
