@@ -307,6 +307,26 @@ struct PogsAmdMany {
   std::unique_ptr<ManyHandle> impl;
 };
 
+namespace {
+// What every create entry ends with: a new handle around the implementation `make()` builds, handed to *out only once
+// that exists (a throw on the way leaves *out NULL and nothing behind).
+template <typename Handle, typename Make>
+void new_handle(Handle **out, Make make) {
+  std::unique_ptr<Handle> h(new Handle);
+  h->impl.reset(make());
+  *out = h.release();
+}
+
+// What every many-problem entry refuses first: an empty call, then any projector but the direct one (`what`: the
+// prefix of the two messages).
+void check_many_call(const std::string &what, int k, const PogsAmdOptions *opt) {
+  POGS_CHECK(k >= 1, (what + ": k must be >= 1").c_str());
+  const int projector = opt ? opt->projector : POGS_AMD_PROJ_DEFAULT;
+  POGS_CHECK(projector == POGS_AMD_PROJ_DEFAULT || projector == POGS_AMD_PROJ_DIRECT,
+             (what + ": only the direct projector is supported (CGLS refused)").c_str());
+}
+}  // namespace
+
 extern "C" {
 
 int PogsD(enum ORD ord, size_t m, size_t n, const double *A, const double *f_a, const double *f_b,
@@ -363,9 +383,7 @@ int PogsAmdCreateDense(PogsAmdSolver **out, int dtype, enum ORD ord, size_t m, s
     *out = nullptr;
     check_dense_storage(dtype, m, n, opt, dist);   // refused before anything is built
     DeviceGuard guard(opt ? opt->device : -1);   // the caller's current device is put back on exit
-    std::unique_ptr<PogsAmdSolver> h(new PogsAmdSolver);
-    h->impl.reset(make_dense_solver(dtype, ord, m, n, A, mem, opt, dist));
-    *out = h.release();
+    new_handle(out, [&] { return make_dense_solver(dtype, ord, m, n, A, mem, opt, dist); });
     return 0;
   });
 }
@@ -380,9 +398,7 @@ int PogsAmdCreateSparse(PogsAmdSolver **out, int dtype, enum ORD ord, size_t m, 
                "POGS_AMD_PROJ_CGLS_FUSED is a dense projector (a sparse handle: POGS_AMD_PROJ_CGLS runs the device-resident loop)");
     POGS_CHECK(!(opt && PogsAmdOptStorage(opt) != POGS_AMD_STORE_SAME), "storage: a sparse handle stores its matrix in its dtype (POGS_AMD_STORE_SAME)");
     DeviceGuard guard(opt ? opt->device : -1);
-    std::unique_ptr<PogsAmdSolver> h(new PogsAmdSolver);
-    h->impl.reset(make_sparse_solver(dtype, ord, m, n, nnz, data, ptr, ind, mem, opt, dist));
-    *out = h.release();
+    new_handle(out, [&] { return make_sparse_solver(dtype, ord, m, n, nnz, data, ptr, ind, mem, opt, dist); });
     return 0;
   });
 }
@@ -406,9 +422,8 @@ int PogsAmdCreateSparseMixed(PogsAmdSolver **out, enum ORD ord, size_t m, size_t
                  "storage: unknown value (a mixed sparse handle takes 0 or POGS_AMD_STORE_F32; it stores float non-zeros either way)");
     }
     DeviceGuard guard(opt ? opt->device : -1);
-    std::unique_ptr<PogsAmdSolver> h(new PogsAmdSolver);
-    h->impl.reset(make_sparse_solver_mixed(static_cast<int>(ord), m, n, nnz, data, ptr, ind, mem, opt));
-    *out = h.release();
+    new_handle(out,
+               [&] { return make_sparse_solver_mixed(static_cast<int>(ord), m, n, nnz, data, ptr, ind, mem, opt); });
     return 0;
   });
 }
@@ -523,10 +538,7 @@ int PogsAmdSolveManyFn(int dtype, enum ORD ord, int k, size_t m, size_t n, const
                        int gap_stop, void *x, void *y, void *l, void *mu, double *optval, unsigned int *final_iter,
                        int *status) {
   return guarded([&]() {
-    POGS_CHECK(k >= 1, "many-problem solve: k must be >= 1");
-    const int projector = opt ? opt->projector : POGS_AMD_PROJ_DEFAULT;
-    POGS_CHECK(projector == POGS_AMD_PROJ_DEFAULT || projector == POGS_AMD_PROJ_DIRECT,
-               "many-problem solve: only the direct projector is supported (CGLS refused)");
+    check_many_call("many-problem solve", k, opt);
     const int device = opt ? opt->device : -1;
     const auto fg = fn_hosts("many-problem solve", k, f, g, x, final_iter, status);
     DeviceGuard guard(device);
@@ -542,13 +554,9 @@ int PogsAmdManyCreate(PogsAmdMany **out, int dtype, enum ORD ord, int k, size_t 
   return guarded([&]() {
     POGS_CHECK(out != nullptr, "many-problem handle: null out");
     *out = nullptr;
-    POGS_CHECK(k >= 1, "many-problem solve: k must be >= 1");
-    const int projector = opt ? opt->projector : POGS_AMD_PROJ_DEFAULT;
-    POGS_CHECK(projector == POGS_AMD_PROJ_DEFAULT || projector == POGS_AMD_PROJ_DIRECT,
-               "many-problem solve: only the direct projector is supported (CGLS refused)");
-    std::unique_ptr<PogsAmdMany> h(new PogsAmdMany);
-    h->impl.reset(many_create(dtype, static_cast<int>(ord), k, m, n, A, mem, opt ? opt->device : -1));
-    *out = h.release();
+    check_many_call("many-problem solve", k, opt);
+    const int device = opt ? opt->device : -1;
+    new_handle(out, [&] { return many_create(dtype, static_cast<int>(ord), k, m, n, A, mem, device); });
     return 0;
   });
 }
@@ -559,10 +567,7 @@ int PogsAmdSolveManyRaggedFn(int dtype, enum ORD ord, int k, const size_t *m, co
                              int adaptive_rho, int gap_stop, void *x, void *y, void *l, void *mu, double *optval,
                              unsigned int *final_iter, int *status) {
   return guarded([&]() {
-    POGS_CHECK(k >= 1, "ragged many-problem solve: k must be >= 1");
-    const int projector = opt ? opt->projector : POGS_AMD_PROJ_DEFAULT;
-    POGS_CHECK(projector == POGS_AMD_PROJ_DEFAULT || projector == POGS_AMD_PROJ_DIRECT,
-               "ragged many-problem solve: only the direct projector is supported (CGLS refused)");
+    check_many_call("ragged many-problem solve", k, opt);
     const int device = opt ? opt->device : -1;
     many_check_ragged(dtype, static_cast<int>(ord), k, m, n, A, mem);
     const auto fg = fn_hosts("ragged many-problem solve", k, f, g, x, final_iter, status);
@@ -579,13 +584,9 @@ int PogsAmdManyCreateRagged(PogsAmdMany **out, int dtype, enum ORD ord, int k, c
   return guarded([&]() {
     POGS_CHECK(out != nullptr, "many-problem handle: null out");
     *out = nullptr;
-    POGS_CHECK(k >= 1, "ragged many-problem solve: k must be >= 1");
-    const int projector = opt ? opt->projector : POGS_AMD_PROJ_DEFAULT;
-    POGS_CHECK(projector == POGS_AMD_PROJ_DEFAULT || projector == POGS_AMD_PROJ_DIRECT,
-               "ragged many-problem solve: only the direct projector is supported (CGLS refused)");
-    std::unique_ptr<PogsAmdMany> h(new PogsAmdMany);
-    h->impl.reset(many_create_ragged(dtype, static_cast<int>(ord), k, m, n, A, mem, opt ? opt->device : -1));
-    *out = h.release();
+    check_many_call("ragged many-problem solve", k, opt);
+    const int device = opt ? opt->device : -1;
+    new_handle(out, [&] { return many_create_ragged(dtype, static_cast<int>(ord), k, m, n, A, mem, device); });
     return 0;
   });
 }

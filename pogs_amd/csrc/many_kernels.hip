@@ -1264,22 +1264,35 @@ class ManyHandleT : public ManyHandle {
 
 }  // namespace
 
+// The argument checks of every many-problem entry, `what` the prefix of their messages, in the order the entries
+// report them: the call (dtype, k, ord, mem), then A and one shape's envelope.  A ragged entry checks its call the same
+// way and words the rest per problem.
+namespace {
+void many_check_call(const std::string &what, int dtype, int ord, int k, int mem) {
+  POGS_CHECK(dtype == POGS_AMD_F32 || dtype == POGS_AMD_F64, (what + ": unknown dtype").c_str());
+  POGS_CHECK(k >= 1, (what + ": k must be >= 1").c_str());
+  POGS_CHECK(ord == ROW_MAJ || ord == COL_MAJ, (what + ": unknown ord").c_str());
+  POGS_CHECK(mem == POGS_AMD_HOST || mem == POGS_AMD_DEVICE, (what + ": unknown mem").c_str());
+}
+
+void many_check_uniform(const std::string &what, int dtype, int ord, int k, size_t m, size_t n, const void *A,
+                        int mem) {
+  many_check_call(what, dtype, ord, k, mem);
+  POGS_CHECK(A != nullptr, (what + ": null A").c_str());
+  POGS_CHECK(m >= 1 && n >= 1, (what + ": m and n must be >= 1").c_str());
+  POGS_CHECK(std::min(m, n) <= POGS_AMD_MANY_MIN_DIM_MAX,
+             (what + ": min(m, n) exceeds POGS_AMD_MANY_MIN_DIM_MAX").c_str());
+  POGS_CHECK(std::max(m, n) <= POGS_AMD_MANY_MAX_DIM_MAX,
+             (what + ": max(m, n) exceeds POGS_AMD_MANY_MAX_DIM_MAX").c_str());
+}
+}  // namespace
+
 void many_check_args(int dtype, int ord, int k, size_t m, size_t n, const void *A, int mem) {
-  POGS_CHECK(dtype == POGS_AMD_F32 || dtype == POGS_AMD_F64, "many-problem solve: unknown dtype");
-  POGS_CHECK(k >= 1, "many-problem solve: k must be >= 1");
-  POGS_CHECK(ord == ROW_MAJ || ord == COL_MAJ, "many-problem solve: unknown ord");
-  POGS_CHECK(mem == POGS_AMD_HOST || mem == POGS_AMD_DEVICE, "many-problem solve: unknown mem");
-  POGS_CHECK(A != nullptr, "many-problem solve: null A");
-  POGS_CHECK(m >= 1 && n >= 1, "many-problem solve: m and n must be >= 1");
-  POGS_CHECK(std::min(m, n) <= POGS_AMD_MANY_MIN_DIM_MAX, "many-problem solve: min(m, n) exceeds POGS_AMD_MANY_MIN_DIM_MAX");
-  POGS_CHECK(std::max(m, n) <= POGS_AMD_MANY_MAX_DIM_MAX, "many-problem solve: max(m, n) exceeds POGS_AMD_MANY_MAX_DIM_MAX");
+  many_check_uniform("many-problem solve", dtype, ord, k, m, n, A, mem);
 }
 
 void many_check_ragged(int dtype, int ord, int k, const size_t *m, const size_t *n, const void *A, int mem) {
-  POGS_CHECK(dtype == POGS_AMD_F32 || dtype == POGS_AMD_F64, "ragged many-problem solve: unknown dtype");
-  POGS_CHECK(k >= 1, "ragged many-problem solve: k must be >= 1");
-  POGS_CHECK(ord == ROW_MAJ || ord == COL_MAJ, "ragged many-problem solve: unknown ord");
-  POGS_CHECK(mem == POGS_AMD_HOST || mem == POGS_AMD_DEVICE, "ragged many-problem solve: unknown mem");
+  many_check_call("ragged many-problem solve", dtype, ord, k, mem);
   POGS_CHECK(m != nullptr && n != nullptr, "ragged many-problem solve: null m or n");
   POGS_CHECK(A != nullptr, "ragged many-problem solve: null A");
   for (int j = 0; j < k; ++j) {
@@ -1355,14 +1368,7 @@ void solve_many(int dtype, int ord, int k, size_t m, size_t n, const void *A, in
 
 void many_setup_check(int dtype, int ord, int k, size_t m, size_t n, const void *A, int mem, void *A_eq, void *d,
                       void *e, double *nrmA, void *W) {
-  POGS_CHECK(dtype == POGS_AMD_F32 || dtype == POGS_AMD_F64, "many setup check: unknown dtype");
-  POGS_CHECK(k >= 1, "many setup check: k must be >= 1");
-  POGS_CHECK(ord == ROW_MAJ || ord == COL_MAJ, "many setup check: unknown ord");
-  POGS_CHECK(mem == POGS_AMD_HOST || mem == POGS_AMD_DEVICE, "many setup check: unknown mem");
-  POGS_CHECK(A != nullptr, "many setup check: null A");
-  POGS_CHECK(m >= 1 && n >= 1, "many setup check: m and n must be >= 1");
-  POGS_CHECK(std::min(m, n) <= POGS_AMD_MANY_MIN_DIM_MAX, "many setup check: min(m, n) exceeds POGS_AMD_MANY_MIN_DIM_MAX");
-  POGS_CHECK(std::max(m, n) <= POGS_AMD_MANY_MAX_DIM_MAX, "many setup check: max(m, n) exceeds POGS_AMD_MANY_MAX_DIM_MAX");
+  many_check_uniform("many setup check", dtype, ord, k, m, n, A, mem);
   if (dtype == POGS_AMD_F64)
     many_setup_check_t<double>(ord, k, m, n, A, mem, static_cast<double *>(A_eq), static_cast<double *>(d),
                                static_cast<double *>(e), nrmA, static_cast<double *>(W));

@@ -404,19 +404,130 @@ def _fn_struct(f, count, dtype, keep):
     return st
 
 
+def _counted(who, k, fs, gs):
+    """``fs`` and ``gs`` as lists, after the check that each holds one function vector per problem."""
+    fs, gs = list(fs), list(gs)
+    if len(fs) != k or len(gs) != k:
+        raise ValueError("%s: %d matrices, %d f and %d g function vectors" % (who, k, len(fs), len(gs)))
+    return fs, gs
+
+
+def _fn_arrays(who, fs, gs, shapes, dtype, each=False):
+    """The function pairs of the len(shapes) problems of a call as two PogsAmdFn arrays plus their keep-alive list,
+    after the count check and every length check.  ``shapes``: the pairs (m_j, n_j); ``each``: they differ from
+    problem to problem, and a length message names its problem."""
+    k = len(shapes)
+    fs, gs = _counted(who, k, fs, gs)
+    keep = []
+    fa = (_lib.PogsAmdFn * k)()
+    ga = (_lib.PogsAmdFn * k)()
+    for j, (m, n) in enumerate(shapes):
+        if len(fs[j]) != m or len(gs[j]) != n:
+            raise ValueError("%s: %sf must have length %d and g length %d, got %d and %d"
+                             % (who, "problem %d: " % j if each else "", m, n, len(fs[j]), len(gs[j])))
+        fa[j] = _fn_struct(fs[j], m, dtype, keep)
+        ga[j] = _fn_struct(gs[j], n, dtype, keep)
+    return fa, ga, keep
+
+
+def _rho_vector(who, rho, k):
+    """``rho``, one value or k values, as k float64 values."""
+    rhos = np.full(k, float(rho)) if np.ndim(rho) == 0 else np.ascontiguousarray(rho, dtype=np.float64).ravel()
+    if len(rhos) != k:
+        raise ValueError("%s: %d problems and %d rho values" % (who, k, len(rhos)))
+    return rhos
+
+
+def _tail(abs_tol, rel_tol, max_iter, verbose, adaptive_rho, gap_stop):
+    """The scalars every solve entry takes after rho (and the starts), as the ABI takes them."""
+    return abs_tol, rel_tol, int(max_iter), int(verbose), int(adaptive_rho), int(gap_stop)
+
+
+def _code(dt):
+    return _lib.F64 if dt == np.float64 else _lib.F32
+
+
+def _direct_options(tdev, device):
+    """The options of a many-problem call: the direct projector on ``device``, -1 meaning a device tensor's own."""
+    return _lib.PogsAmdOptions(device=tdev if (device == -1 and tdev is not None) else device,
+                               projector=_lib.PROJ_DIRECT)
+
+
+def _ragged_split(flat, lens):
+    """The per-problem pieces (copies) of a packed output."""
+    ends = np.cumsum(lens)
+    return [flat[e - n:e].copy() for e, n in zip(ends, lens)]
+
+
+class _Outputs:
+    """The output buffers of a k-problem call.  ``m``, ``n``: the one shape of a uniform call, whose x, mu are k x n
+    and y, l k x m arrays, or the k m_j and n_j of a ragged call, whose outputs are packed problem after problem."""
+
+    def __init__(self, dt, k, m, n, rho=False):
+        self.ragged, self.k, self.m, self.n = np.ndim(m) > 0, k, m, n
+        rows, cols = (int(sum(m)), int(sum(n))) if self.ragged else ((k, m), (k, n))
+        self.x, self.mu = np.zeros(cols, dt), np.zeros(cols, dt)
+        self.y, self.l = np.zeros(rows, dt), np.zeros(rows, dt)
+        self.optval = np.zeros(k, np.float64)
+        self.final_iter = np.zeros(k, np.uint32)
+        self.status = np.zeros(k, np.int32)
+        self.rho = np.zeros(k, np.float64) if rho else None      # the final rho, of an entry that returns it
+
+    def pointers(self):
+        """The seven output pointers in ABI order, then rho_final where the entry has one."""
+        out = [self.x, self.y, self.l, self.mu, self.optval, self.final_iter, self.status]
+        return [_ptr(a) for a in (out if self.rho is None else out + [self.rho])]
+
+    def _vectors(self):
+        """x, y, l, mu, each indexed by problem: the k x n / k x m arrays, or lists of copies of the ragged pieces."""
+        if not self.ragged:
+            return self.x, self.y, self.l, self.mu
+        return (_ragged_split(self.x, self.n), _ragged_split(self.y, self.m), _ragged_split(self.l, self.m),
+                _ragged_split(self.mu, self.n))
+
+    def arrays(self):
+        """One dictionary for the call: arrays with a row per problem (ragged: lists with a piece per problem)."""
+        x, y, l, mu = self._vectors()
+        res = {"x": x, "y": y, "l": l, "mu": mu, "optval": self.optval, "iterations": self.final_iter.astype(np.int64),
+               "status": self.status.astype(np.int64)}
+        if self.rho is not None:
+            res["rho"] = self.rho
+        return res
+
+    def problems(self):
+        """One dictionary per problem, with the keys `Solver.solve` returns (and "rho")."""
+        x, y, l, mu = self._vectors()
+        res = [{"x": x[j], "y": y[j], "l": l[j], "mu": mu[j], "optval": float(self.optval[j]),
+                "iterations": int(self.final_iter[j]), "status": int(self.status[j])} for j in range(self.k)]
+        if self.rho is not None:
+            for j, r in enumerate(res):
+                r["rho"] = float(self.rho[j])
+        return res
+
+
+def _is_tensor(a):
+    return hasattr(a, "data_ptr") and hasattr(a, "is_cuda")
+
+
+def _tensor_dtype(who, A, dtype):
+    """The solve's dtype for a torch tensor, which is read in place: the tensor's own; ``dtype`` may only repeat it."""
+    import torch
+
+    tdt = {torch.float32: np.float32, torch.float64: np.float64}.get(A.dtype)
+    if tdt is None:
+        raise ValueError("%s: A must be float32 or float64" % who)
+    dt = _resolve_dtype(tdt if dtype is None else dtype)
+    if dt != np.dtype(tdt):
+        raise ValueError("%s: a device tensor is read in place: its dtype must be the solve's dtype" % who)
+    return dt
+
+
 def _many_matrices(A, dtype):
     """(k, m, n, pointer, mem, ord, dtype, device, keep-alive) of the k matrices of `solve_many`."""
-    if hasattr(A, "data_ptr") and hasattr(A, "is_cuda"):          # a torch tensor
-        import torch
-
+    if _is_tensor(A):
         if A.dim() != 3:
             raise ValueError("solve_many: A must be a (k, m, n) tensor, got %d dimensions" % A.dim())
-        tdt = {torch.float32: np.float32, torch.float64: np.float64}.get(A.dtype)
-        if tdt is None:
-            raise ValueError("solve_many: A must be float32 or float64")
-        dt = _resolve_dtype(tdt if dtype is None else dtype)
-        if dt != np.dtype(tdt):
-            raise ValueError("solve_many: a device tensor is read in place: its dtype must be the solve's dtype")
+        dt = _tensor_dtype("solve_many", A, dtype)
         k, m, n = A.shape
         if not A.is_cuda:
             return _many_matrices(A.numpy(), dt)
@@ -464,42 +575,17 @@ def solve_many(A, fs, gs, rho=1.0, abs_tol=1e-4, rel_tol=1e-4, max_iter=2500, ve
     current one.  Returns {'x': k x n, 'y': k x m, 'l': k x m, 'mu': k x n, 'optval', 'iterations', 'status':
     length k}.  verbose > 0 prints one summary for the call."""
     k, m, n, aptr, mem, order, dt, tdev, keep_a = _many_matrices(A, dtype)
-    fs, gs = list(fs), list(gs)
-    if len(fs) != k or len(gs) != k:
-        raise ValueError("solve_many: %d matrices, %d f and %d g function vectors" % (k, len(fs), len(gs)))
-    if np.ndim(rho) == 0:
-        rhos = np.full(k, float(rho))
-    else:
-        rhos = np.ascontiguousarray(rho, dtype=np.float64).ravel()
-        if len(rhos) != k:
-            raise ValueError("solve_many: %d problems and %d rho values" % (k, len(rhos)))
-    keep = []
-    fa = (_lib.PogsAmdFn * k)()
-    ga = (_lib.PogsAmdFn * k)()
-    for j in range(k):
-        if len(fs[j]) != m or len(gs[j]) != n:
-            raise ValueError("solve_many: f must have length %d and g length %d, got %d and %d"
-                             % (m, n, len(fs[j]), len(gs[j])))
-        fa[j] = _fn_struct(fs[j], m, dt, keep)
-        ga[j] = _fn_struct(gs[j], n, dt, keep)
-    dev = tdev if (device == -1 and tdev is not None) else device
-    opt = _lib.PogsAmdOptions(device=dev, projector=_lib.PROJ_DIRECT)
-    x = np.zeros((k, n), dt)
-    y = np.zeros((k, m), dt)
-    l = np.zeros((k, m), dt)
-    mu = np.zeros((k, n), dt)
-    optval = np.zeros(k, np.float64)
-    final_iter = np.zeros(k, np.uint32)
-    status = np.zeros(k, np.int32)
-    code = _lib.F64 if dt == np.float64 else _lib.F32
-    st = lib.PogsAmdSolveManyFn(code, int(order), k, m, n, aptr, mem, ctypes.byref(opt), fa, ga, _ptr(rhos), abs_tol,
-                                rel_tol, int(max_iter), int(verbose), int(adaptive_rho), int(gap_stop), _ptr(x), _ptr(y),
-                                _ptr(l), _ptr(mu), _ptr(optval), _ptr(final_iter), _ptr(status))
+    fs, gs = _counted("solve_many", k, fs, gs)          # (before rho; a ragged call checks rho first)
+    rhos = _rho_vector("solve_many", rho, k)
+    fa, ga, keep = _fn_arrays("solve_many", fs, gs, [(m, n)] * k, dt)
+    opt = _direct_options(tdev, device)
+    out = _Outputs(dt, k, m, n)
+    st = lib.PogsAmdSolveManyFn(_code(dt), int(order), k, m, n, aptr, mem, ctypes.byref(opt), fa, ga, _ptr(rhos),
+                                *_tail(abs_tol, rel_tol, max_iter, verbose, adaptive_rho, gap_stop), *out.pointers())
     del keep, keep_a
     if st != 0:
         raise RuntimeError("pogs_amd: many-problem solve failed: " + _lib.last_error())
-    return {"x": x, "y": y, "l": l, "mu": mu, "optval": optval, "iterations": final_iter.astype(np.int64),
-            "status": status.astype(np.int64)}
+    return out.arrays()
 
 
 def _ragged_matrices(As, dtype, shapes, order, who):
@@ -508,24 +594,14 @@ def _ragged_matrices(As, dtype, shapes, order, who):
     if order not in ("C", "F"):
         raise ValueError("%s: order must be 'C' or 'F', got %r" % (who, order))
 
-    def is_tensor(a):
-        return hasattr(a, "data_ptr") and hasattr(a, "is_cuda")
-
     if shapes is not None:                                        # one packed buffer
         shp = [tuple(int(v) for v in s) for s in shapes]
         if not shp or any(len(s) != 2 or s[0] < 1 or s[1] < 1 for s in shp):
             raise ValueError("%s: shapes must be k >= 1 pairs (m_j, n_j) of positive sizes" % who)
         total = sum(m * n for m, n in shp)
         ordc = Ordering.ROW_MAJ if order == "C" else Ordering.COL_MAJ
-        if is_tensor(As):
-            import torch
-
-            tdt = {torch.float32: np.float32, torch.float64: np.float64}.get(As.dtype)
-            if tdt is None:
-                raise ValueError("%s: A must be float32 or float64" % who)
-            dt = _resolve_dtype(tdt if dtype is None else dtype)
-            if dt != np.dtype(tdt):
-                raise ValueError("%s: a device tensor is read in place: its dtype must be the solve's dtype" % who)
+        if _is_tensor(As):
+            dt = _tensor_dtype(who, As, dtype)
             if As.dim() != 1 or As.numel() != total or not As.is_contiguous():
                 raise ValueError("%s: a packed A must be one contiguous 1-D tensor of sum m_j n_j = %d elements"
                                  % (who, total))
@@ -541,12 +617,12 @@ def _ragged_matrices(As, dtype, shapes, order, who):
         arr = np.ascontiguousarray(arr, dtype=dt)
         return len(shp), [s[0] for s in shp], [s[1] for s in shp], _ptr(arr), _lib.HOST, ordc, dt, None, arr
 
-    if is_tensor(As) or isinstance(As, np.ndarray) or not hasattr(As, "__len__"):
+    if _is_tensor(As) or isinstance(As, np.ndarray) or not hasattr(As, "__len__"):
         raise ValueError("%s: As must be a sequence of 2-D arrays (or one packed array with shapes=...)" % who)
     mats = list(As)
     if not mats:
         raise ValueError("%s: As must hold k >= 1 matrices" % who)
-    if all(is_tensor(a) for a in mats) and all(a.is_cuda for a in mats):
+    if all(_is_tensor(a) for a in mats) and all(a.is_cuda for a in mats):
         import torch
 
         if any(a.dim() != 2 for a in mats):
@@ -558,7 +634,7 @@ def _ragged_matrices(As, dtype, shapes, order, who):
             raise ValueError("%s: every member of As must have at least one row and one column" % who)
         packed = torch.cat([a.contiguous().reshape(-1) for a in mats])   # packed on the device, row-major
         return _ragged_matrices(packed, dtype, shp, "C", who)
-    mats = [a.detach().cpu().numpy() if is_tensor(a) else np.asarray(a) for a in mats]
+    mats = [a.detach().cpu().numpy() if _is_tensor(a) else np.asarray(a) for a in mats]
     if any(a.ndim != 2 for a in mats):
         raise ValueError("%s: every member of As must be two-dimensional, got %s"
                          % (who, [a.ndim for a in mats if a.ndim != 2]))
@@ -571,29 +647,6 @@ def _ragged_matrices(As, dtype, shapes, order, who):
     flat = np.concatenate([np.asarray(a, dtype=dt).ravel(order="F" if fortran else "C") for a in mats])
     return (len(mats), [a.shape[0] for a in mats], [a.shape[1] for a in mats], _ptr(flat), _lib.HOST,
             Ordering.COL_MAJ if fortran else Ordering.ROW_MAJ, dt, None, flat)
-
-
-def _ragged_functions(who, fs, gs, ms, ns, dt, keep):
-    """The PogsAmdFn arrays of a ragged call after the count and length checks."""
-    k = len(ms)
-    fs, gs = list(fs), list(gs)
-    if len(fs) != k or len(gs) != k:
-        raise ValueError("%s: %d matrices, %d f and %d g function vectors" % (who, k, len(fs), len(gs)))
-    fa = (_lib.PogsAmdFn * k)()
-    ga = (_lib.PogsAmdFn * k)()
-    for j in range(k):
-        if len(fs[j]) != ms[j] or len(gs[j]) != ns[j]:
-            raise ValueError("%s: problem %d: f must have length %d and g length %d, got %d and %d"
-                             % (who, j, ms[j], ns[j], len(fs[j]), len(gs[j])))
-        fa[j] = _fn_struct(fs[j], ms[j], dt, keep)
-        ga[j] = _fn_struct(gs[j], ns[j], dt, keep)
-    return fa, ga
-
-
-def _ragged_split(flat, lens):
-    """The per-problem pieces (copies) of a packed output."""
-    ends = np.cumsum(lens)
-    return [flat[e - n:e].copy() for e, n in zip(ends, lens)]
 
 
 def solve_many_ragged(As, fs, gs, rho=1.0, abs_tol=1e-4, rel_tol=1e-4, max_iter=2500, verbose=0, adaptive_rho=True,
@@ -610,34 +663,19 @@ def solve_many_ragged(As, fs, gs, rho=1.0, abs_tol=1e-4, rel_tol=1e-4, max_iter=
     Returns a list of k dictionaries {'x': n_j, 'y': m_j, 'l': m_j, 'mu': n_j, 'optval', 'iterations', 'status'}."""
     who = "solve_many_ragged"
     k, ms, ns, aptr, mem, ordc, dt, tdev, keep_a = _ragged_matrices(As, dtype, shapes, order, who)
-    if np.ndim(rho) == 0:
-        rhos = np.full(k, float(rho))
-    else:
-        rhos = np.ascontiguousarray(rho, dtype=np.float64).ravel()
-        if len(rhos) != k:
-            raise ValueError("%s: %d problems and %d rho values" % (who, k, len(rhos)))
-    keep = []
-    fa, ga = _ragged_functions(who, fs, gs, ms, ns, dt, keep)
-    dev = tdev if (device == -1 and tdev is not None) else device
-    opt = _lib.PogsAmdOptions(device=dev, projector=_lib.PROJ_DIRECT)
-    M, N = int(sum(ms)), int(sum(ns))
-    x, mu = np.zeros(N, dt), np.zeros(N, dt)
-    y, l = np.zeros(M, dt), np.zeros(M, dt)
-    optval = np.zeros(k, np.float64)
-    final_iter = np.zeros(k, np.uint32)
-    status = np.zeros(k, np.int32)
+    rhos = _rho_vector(who, rho, k)
+    fa, ga, keep = _fn_arrays(who, fs, gs, list(zip(ms, ns)), dt, each=True)
+    opt = _direct_options(tdev, device)
+    out = _Outputs(dt, k, ms, ns)
     marr = (ctypes.c_size_t * k)(*ms)
     narr = (ctypes.c_size_t * k)(*ns)
-    code = _lib.F64 if dt == np.float64 else _lib.F32
-    st = lib.PogsAmdSolveManyRaggedFn(code, int(ordc), k, marr, narr, aptr, mem, ctypes.byref(opt), fa, ga, _ptr(rhos),
-                                      abs_tol, rel_tol, int(max_iter), int(verbose), int(adaptive_rho), int(gap_stop),
-                                      _ptr(x), _ptr(y), _ptr(l), _ptr(mu), _ptr(optval), _ptr(final_iter), _ptr(status))
+    st = lib.PogsAmdSolveManyRaggedFn(_code(dt), int(ordc), k, marr, narr, aptr, mem, ctypes.byref(opt), fa, ga,
+                                      _ptr(rhos), *_tail(abs_tol, rel_tol, max_iter, verbose, adaptive_rho, gap_stop),
+                                      *out.pointers())
     del keep, keep_a
     if st != 0:
         raise RuntimeError("pogs_amd: ragged many-problem solve failed: " + _lib.last_error())
-    xs, mus, ys, ls = _ragged_split(x, ns), _ragged_split(mu, ns), _ragged_split(y, ms), _ragged_split(l, ms)
-    return [{"x": xs[j], "y": ys[j], "l": ls[j], "mu": mus[j], "optval": float(optval[j]),
-             "iterations": int(final_iter[j]), "status": int(status[j])} for j in range(k)]
+    return out.problems()
 
 
 def solve_ridge(A, b, lambd, abs_tol=1e-4, rel_tol=1e-4, max_iter=2500, verbose=0, rho=1.0, dtype=None):
@@ -744,7 +782,7 @@ class Solver:
                 raise ValueError("values=float32 is the sparse option; a dense matrix takes storage=np.float32")
             self.storage = STORE_F32
         self._h = ctypes.c_void_p()
-        code = _lib.F64 if self.dtype == np.float64 else _lib.F32
+        code = _code(self.dtype)
         opt = _lib.PogsAmdOptions(device=device, projector=projector, profile=int(profile), storage=self.storage)
         dist_s = None
         self._m_global = None   # row shards: the rows of the whole matrix
@@ -756,6 +794,7 @@ class Solver:
             assert len(uid) == _lib.UNIQUE_ID_BYTES
             # (a c_char array field reads back as an immutable bytes copy: write through the address)
             ctypes.memmove(ctypes.addressof(dist_s) + _lib.PogsAmdDist.unique_id.offset, uid, _lib.UNIQUE_ID_BYTES)
+        dist_p = ctypes.byref(dist_s) if dist_s is not None else None
         if device_ptr:
             _lib.check_device_pointer_interop()
         self.sparse = (not device_ptr) and HAS_SCIPY and sp.issparse(A)
@@ -765,28 +804,20 @@ class Solver:
             self.sparse = True
             self.m, self.n = shape
             dptr, pptr, iptr, nnz = (int(v) for v in A)
-            if mixed_values:
-                st = lib.PogsAmdCreateSparseMixed(ctypes.byref(self._h), int(Ordering.ROW_MAJ), self.m, self.n, nnz,
-                                                  ctypes.c_void_p(dptr), ctypes.c_void_p(pptr), ctypes.c_void_p(iptr),
-                                                  _lib.DEVICE, ctypes.byref(opt))
-            else:
-                st = lib.PogsAmdCreateSparse(ctypes.byref(self._h), code, int(Ordering.ROW_MAJ), self.m, self.n, nnz,
-                                             ctypes.c_void_p(dptr), ctypes.c_void_p(pptr), ctypes.c_void_p(iptr),
-                                             _lib.DEVICE, ctypes.byref(opt),
-                                             ctypes.byref(dist_s) if dist_s is not None else None)
+            csr, mem = (ctypes.c_void_p(dptr), ctypes.c_void_p(pptr), ctypes.c_void_p(iptr)), _lib.DEVICE
         elif self.sparse:
             A_csr = sp.csr_matrix(A, dtype=self.dtype)
             self.m, self.n = A_csr.shape
             data = np.ascontiguousarray(A_csr.data, dtype=self.dtype)
             ptr = np.ascontiguousarray(A_csr.indptr, dtype=np.int32)
             ind = np.ascontiguousarray(A_csr.indices, dtype=np.int32)
+            csr, nnz, mem = (_ptr(data), _ptr(ptr), _ptr(ind)), A_csr.nnz, _lib.HOST
+        if self.sparse:
+            matrix = (int(Ordering.ROW_MAJ), self.m, self.n, nnz, *csr, mem, ctypes.byref(opt))
             if mixed_values:
-                st = lib.PogsAmdCreateSparseMixed(ctypes.byref(self._h), int(Ordering.ROW_MAJ), self.m, self.n, A_csr.nnz,
-                                                  _ptr(data), _ptr(ptr), _ptr(ind), _lib.HOST, ctypes.byref(opt))
+                st = lib.PogsAmdCreateSparseMixed(ctypes.byref(self._h), *matrix)
             else:
-                st = lib.PogsAmdCreateSparse(ctypes.byref(self._h), code, int(Ordering.ROW_MAJ), self.m, self.n,
-                                             A_csr.nnz, _ptr(data), _ptr(ptr), _ptr(ind), _lib.HOST, ctypes.byref(opt),
-                                             ctypes.byref(dist_s) if dist_s is not None else None)
+                st = lib.PogsAmdCreateSparse(ctypes.byref(self._h), code, *matrix, dist_p)
         else:
             if device_ptr:
                 self.m, self.n = shape
@@ -796,7 +827,7 @@ class Solver:
                 self.m, self.n = A.shape
                 ptr_val, mem = _ptr(A), _lib.HOST
             st = lib.PogsAmdCreateDense(ctypes.byref(self._h), code, int(order), self.m, self.n, ptr_val, mem,
-                                        ctypes.byref(opt), ctypes.byref(dist_s) if dist_s is not None else None)
+                                        ctypes.byref(opt), dist_p)
         if st != 0:
             raise RuntimeError("pogs_amd: solver creation failed: " + _lib.last_error())
         _LIVE_SOLVERS.add(self)
@@ -805,20 +836,8 @@ class Solver:
         """(f, g) as two PogsAmdFn structures: per-element fields as typed host arrays, fields that are still scalars
         as broadcast values (filled on the device; include/pogs_amd.h: PogsAmdSolveFn).  Returns (structs, keep-alive)."""
         assert len(f) == self.m and len(g) == self.n
-        keep, structs = [], []
-        for fv in (_as_vector(f), _as_vector(g)):
-            st = _lib.PogsAmdFn()
-            for k in FunctionVector._FIELDS:
-                v = fv._v[k]
-                if isinstance(v, np.ndarray):
-                    arr = np.ascontiguousarray(v, dtype=np.int32 if k == "h" else self.dtype)
-                    keep.append(arr)
-                    setattr(st, k, arr.ctypes.data)
-                else:
-                    setattr(st, k, None)
-                    setattr(st, k + "0", int(v) if k == "h" else float(v))
-            structs.append(st)
-        return structs, keep
+        keep = []
+        return [_fn_struct(f, self.m, self.dtype, keep), _fn_struct(g, self.n, self.dtype, keep)], keep
 
     def warm_start(self, x0, l0):
         """Start the next solve from (x0, lambda0) instead of zero (reference: SetInitX /
@@ -840,9 +859,9 @@ class Solver:
         mu = np.zeros(self.n, self.dtype)
         optval = ctypes.c_double()
         final_iter = ctypes.c_uint()
-        status = lib.PogsAmdSolveFn(self._h, ctypes.byref(args[0]), ctypes.byref(args[1]), rho, abs_tol, rel_tol,
-                                    int(max_iter), int(verbose), int(adaptive_rho), int(gap_stop), _ptr(x), _ptr(y),
-                                    _ptr(l), _ptr(mu), ctypes.byref(optval), ctypes.byref(final_iter))
+        status = lib.PogsAmdSolveFn(self._h, ctypes.byref(args[0]), ctypes.byref(args[1]), rho,
+                                    *_tail(abs_tol, rel_tol, max_iter, verbose, adaptive_rho, gap_stop),
+                                    _ptr(x), _ptr(y), _ptr(l), _ptr(mu), ctypes.byref(optval), ctypes.byref(final_iter))
         del keep
         if status == POGS_ERROR:
             raise RuntimeError("pogs_amd: solve failed: " + _lib.last_error())
@@ -864,64 +883,36 @@ class Solver:
         k = len(fs)
         if len(gs) != k:
             raise ValueError("solve_batch: %d f and %d g function vectors" % (k, len(gs)))
-        if np.ndim(rho) == 0:
-            rhos = [float(rho)] * k
-        else:
-            rhos = [float(r) for r in rho]
-            if len(rhos) != k:
-                raise ValueError("solve_batch: %d problems and %d rho values" % (k, len(rhos)))
-        for f, g in zip(fs, gs):
-            if len(f) != self.m or len(g) != self.n:
-                raise ValueError("solve_batch: f must have length %d and g length %d, got %d and %d"
-                                 % (self.m, self.n, len(f), len(g)))
+        rhos = _rho_vector("solve_batch", rho, k)
+        fa, ga, keep = _fn_arrays("solve_batch", fs, gs, [(self.m, self.n)] * k, self.dtype)   # every length, first
         starts = self._batch_starts(k, x0, l0, warm)
         plain = starts is None and not return_rho
         entry = lib.PogsAmdSolveBatchSparseFn if self.sparse else lib.PogsAmdSolveBatchFn
-        out = []
+        tail = _tail(abs_tol, rel_tol, max_iter, verbose, adaptive_rho, gap_stop)
+        res = []
         for lo in range(0, k, _lib.BATCH_MAX):
             hi = min(k, lo + _lib.BATCH_MAX)
             kb = hi - lo
-            fa = (_lib.PogsAmdFn * kb)()
-            ga = (_lib.PogsAmdFn * kb)()
-            keep = []
-            for j in range(kb):
-                (fst, gst), kp = self._coef(fs[lo + j], gs[lo + j])
-                fa[j], ga[j] = fst, gst
-                keep.append(kp)
-            r = np.ascontiguousarray(rhos[lo:hi], dtype=np.float64)
-            x = np.zeros((kb, self.n), self.dtype)
-            y = np.zeros((kb, self.m), self.dtype)
-            l = np.zeros((kb, self.m), self.dtype)
-            mu = np.zeros((kb, self.n), self.dtype)
-            optval = np.zeros(kb, np.float64)
-            final_iter = np.zeros(kb, np.uint32)
-            status = np.zeros(kb, np.int32)
+            # this chunk's structures, in place
+            fb = (_lib.PogsAmdFn * kb).from_buffer(fa, lo * ctypes.sizeof(_lib.PogsAmdFn))
+            gb = (_lib.PogsAmdFn * kb).from_buffer(ga, lo * ctypes.sizeof(_lib.PogsAmdFn))
+            out = _Outputs(self.dtype, kb, self.m, self.n, rho=not plain)
             if plain:
-                st = entry(self._h, kb, fa, ga, _ptr(r), abs_tol, rel_tol, int(max_iter), int(verbose),
-                           int(adaptive_rho), int(gap_stop), _ptr(x), _ptr(y), _ptr(l), _ptr(mu), _ptr(optval),
-                           _ptr(final_iter), _ptr(status))
+                st = entry(self._h, kb, fb, gb, _ptr(rhos[lo:hi]), *tail, *out.pointers())
             else:
-                rho_final = np.zeros(kb, np.float64)
                 xs = ls = flags = None
                 if starts is not None and any(starts[2][lo:hi]):
                     xs = np.ascontiguousarray(starts[0][lo:hi])
                     ls = np.ascontiguousarray(starts[1][lo:hi])
                     flags = np.ascontiguousarray(starts[2][lo:hi], dtype=np.int32)
-                st = lib.PogsAmdSolveBatchWarmFn(self._h, kb, fa, ga, _ptr(r), None if xs is None else _ptr(xs),
-                                                 None if ls is None else _ptr(ls),
-                                                 None if flags is None else _ptr(flags), abs_tol, rel_tol,
-                                                 int(max_iter), int(verbose), int(adaptive_rho), int(gap_stop), _ptr(x),
-                                                 _ptr(y), _ptr(l), _ptr(mu), _ptr(optval), _ptr(final_iter),
-                                                 _ptr(status), _ptr(rho_final))
-            del keep
+                st = lib.PogsAmdSolveBatchWarmFn(self._h, kb, fb, gb, _ptr(rhos[lo:hi]),
+                                                 None if xs is None else _ptr(xs), None if ls is None else _ptr(ls),
+                                                 None if flags is None else _ptr(flags), *tail, *out.pointers())
             if st != 0:
                 raise RuntimeError("pogs_amd: batched solve failed: " + _lib.last_error())
-            for j in range(kb):
-                out.append({"x": x[j], "y": y[j], "l": l[j], "mu": mu[j], "optval": float(optval[j]),
-                            "iterations": int(final_iter[j]), "status": int(status[j])})
-                if not plain:
-                    out[-1]["rho"] = float(rho_final[j])
-        return out
+            res += out.problems()
+        del keep
+        return res
 
     def _batch_starts(self, k, x0, l0, warm):
         """The starts of `solve_batch` as (k x n array, k x m array, k flags), or None when every problem is cold;
@@ -1068,20 +1059,12 @@ class ManySolver:
 
     _STARTS = {"cold": _lib.MANY_COLD, "warm": _lib.MANY_WARM_GIVEN, "last": _lib.MANY_WARM_LAST}
     shapes = None        # a ragged handle (from_ragged): the k pairs (m_j, n_j)
+    _h = None            # until a create entry has been called
 
     def __init__(self, A, dtype=None, device=-1):
-        self._h = ctypes.c_void_p()
-        k, m, n, aptr, mem, order, dt, tdev, keep_a = _many_matrices(A, dtype)
-        self.k, self.m, self.n, self.dtype = k, m, n, np.dtype(dt)
-        dev = tdev if (device == -1 and tdev is not None) else device
-        opt = _lib.PogsAmdOptions(device=dev, projector=_lib.PROJ_DIRECT)
-        code = _lib.F64 if self.dtype == np.float64 else _lib.F32
-        st = lib.PogsAmdManyCreate(ctypes.byref(self._h), code, int(order), k, m, n, aptr, mem, ctypes.byref(opt))
-        del keep_a
-        if st != 0:
-            self._h = ctypes.c_void_p()
-            raise RuntimeError("pogs_amd: many-problem handle creation failed: " + _lib.last_error())
-        _LIVE_SOLVERS.add(self)
+        mats = _many_matrices(A, dtype)
+        self.m, self.n = mats[1], mats[2]
+        self._create(lib.PogsAmdManyCreate, mats, self.m, self.n, device)
 
     @classmethod
     def from_ragged(cls, As, dtype=None, device=-1, shapes=None, order="C"):
@@ -1089,25 +1072,25 @@ class ManySolver:
         ``shapes`` and ``order`` as `solve_many_ragged` takes them.  `solve`, `info` and `close` work as on any
         ManySolver; ``x0`` / ``l0`` are lists of k per-problem arrays, and so are the results' 'x', 'y', 'l', 'mu'.
         ``m`` and ``n`` are the largest m_j and n_j, ``shapes`` the k pairs."""
-        k, ms, ns, aptr, mem, ordc, dt, tdev, keep_a = _ragged_matrices(As, dtype, shapes, order,
-                                                                         "ManySolver.from_ragged")
+        mats = _ragged_matrices(As, dtype, shapes, order, "ManySolver.from_ragged")
+        k, ms, ns = mats[:3]
         self = cls.__new__(cls)
+        self.m, self.n, self.shapes = max(ms), max(ns), list(zip(ms, ns))
+        self._create(lib.PogsAmdManyCreateRagged, mats, (ctypes.c_size_t * k)(*ms), (ctypes.c_size_t * k)(*ns), device)
+        return self
+
+    def _create(self, entry, mats, m, n, device):
+        """What both constructors end with: the call of the create entry on the matrices as `_many_matrices` /
+        `_ragged_matrices` return them, ``m`` and ``n`` as that entry takes them."""
+        k, _, _, aptr, mem, order, dt, tdev, keep_a = mats
         self._h = ctypes.c_void_p()
-        self.k, self.m, self.n, self.dtype = k, max(ms), max(ns), np.dtype(dt)
-        self.shapes = list(zip(ms, ns))
-        dev = tdev if (device == -1 and tdev is not None) else device
-        opt = _lib.PogsAmdOptions(device=dev, projector=_lib.PROJ_DIRECT)
-        code = _lib.F64 if self.dtype == np.float64 else _lib.F32
-        marr = (ctypes.c_size_t * k)(*ms)
-        narr = (ctypes.c_size_t * k)(*ns)
-        st = lib.PogsAmdManyCreateRagged(ctypes.byref(self._h), code, int(ordc), k, marr, narr, aptr, mem,
-                                         ctypes.byref(opt))
-        del keep_a
+        self.k, self.dtype = k, np.dtype(dt)
+        opt = _direct_options(tdev, device)
+        st = entry(ctypes.byref(self._h), _code(self.dtype), int(order), k, m, n, aptr, mem, ctypes.byref(opt))
         if st != 0:
             self._h = ctypes.c_void_p()
             raise RuntimeError("pogs_amd: many-problem handle creation failed: " + _lib.last_error())
         _LIVE_SOLVERS.add(self)
-        return self
 
     def get_shapes(self):
         """The k shapes (m_j, n_j) as the handle reports them (PogsAmdManyGetShapes); either kind of handle."""
@@ -1119,9 +1102,19 @@ class ManySolver:
             raise RuntimeError("pogs_amd: " + _lib.last_error())
         return list(zip(list(marr), list(narr)))
 
-    def _solve_ragged(self, fs, gs, rho, start, x0, l0, abs_tol, rel_tol, max_iter, verbose, adaptive_rho, gap_stop):
+    def _starts(self, x0, l0):
+        """The x0 / l0 of start="warm" as the entry reads them: k x n and k x m, or packed problem after problem."""
         k, dt = self.k, self.dtype
-        ms, ns = [s[0] for s in self.shapes], [s[1] for s in self.shapes]
+        if x0 is None or l0 is None:
+            raise ValueError("ManySolver: start='warm' needs both x0 (k x n) and l0 (k x m)" if self.shapes is None else
+                             "ManySolver: start='warm' needs both x0 and l0 (lists of k per-problem arrays)")
+        if self.shapes is None:
+            x0 = np.ascontiguousarray(x0, dtype=dt)
+            l0 = np.ascontiguousarray(l0, dtype=dt)
+            if x0.shape != (k, self.n) or l0.shape != (k, self.m):
+                raise ValueError("ManySolver: x0 must be %d x %d and l0 %d x %d, got %s and %s"
+                                 % (k, self.n, k, self.m, x0.shape, l0.shape))
+            return x0, l0
 
         def packed(v, lens, name):
             v = list(v)
@@ -1134,37 +1127,7 @@ class ManySolver:
                                      % (name, j, lens[j], a.shape))
             return np.ascontiguousarray(np.concatenate(parts))
 
-        if start == "warm":
-            if x0 is None or l0 is None:
-                raise ValueError("ManySolver: start='warm' needs both x0 and l0 (lists of k per-problem arrays)")
-            x0, l0 = packed(x0, ns, "x0"), packed(l0, ms, "l0")
-        elif x0 is not None or l0 is not None:
-            raise ValueError("ManySolver: x0 / l0 are read with start='warm' only")
-        rhos = None
-        if rho is not None:
-            rhos = np.full(k, float(rho)) if np.ndim(rho) == 0 else np.ascontiguousarray(rho, dtype=np.float64).ravel()
-            if len(rhos) != k:
-                raise ValueError("ManySolver: %d problems and %d rho values" % (k, len(rhos)))
-        keep = []
-        fa, ga = _ragged_functions("ManySolver", fs, gs, ms, ns, dt, keep)
-        M, N = int(sum(ms)), int(sum(ns))
-        x, mu = np.zeros(N, dt), np.zeros(N, dt)
-        y, l = np.zeros(M, dt), np.zeros(M, dt)
-        optval = np.zeros(k, np.float64)
-        final_iter = np.zeros(k, np.uint32)
-        status = np.zeros(k, np.int32)
-        rho_final = np.zeros(k, np.float64)
-        st = lib.PogsAmdManySolveFn(self._h, fa, ga, None if rhos is None else _ptr(rhos), self._STARTS[start],
-                                    None if x0 is None else _ptr(x0), None if l0 is None else _ptr(l0), abs_tol,
-                                    rel_tol, int(max_iter), int(verbose), int(adaptive_rho), int(gap_stop), _ptr(x),
-                                    _ptr(y), _ptr(l), _ptr(mu), _ptr(optval), _ptr(final_iter), _ptr(status),
-                                    _ptr(rho_final))
-        del keep
-        if st != 0:
-            raise RuntimeError("pogs_amd: many-problem solve failed: " + _lib.last_error())
-        return {"x": _ragged_split(x, ns), "y": _ragged_split(y, ms), "l": _ragged_split(l, ms),
-                "mu": _ragged_split(mu, ns), "optval": optval, "iterations": final_iter.astype(np.int64),
-                "status": status.astype(np.int64), "rho": rho_final}
+        return packed(x0, [s[1] for s in self.shapes], "x0"), packed(l0, [s[0] for s in self.shapes], "l0")
 
     def solve(self, fs, gs, rho=None, start="cold", x0=None, l0=None, abs_tol=1e-4, rel_tol=1e-4, max_iter=2500,
               verbose=0, adaptive_rho=True, gap_stop=True):
@@ -1172,60 +1135,31 @@ class ManySolver:
         ``l0``: k x m, the reference's SetInitX + SetInitLambda per problem) or "last" (from each problem's own last
         solution, kept on the device).  ``rho``: None, one value or k values; None means 1.0, and with "last" each
         problem's final rho of the last solve.  Returns `solve_many`'s dictionary plus 'rho', the final rho per
-        problem."""
-        k, m, n, dt = self.k, self.m, self.n, self.dtype
+        problem.  On a ragged handle (`from_ragged`) x0 / l0 and the results' 'x', 'y', 'l', 'mu' are lists of k
+        per-problem arrays."""
+        k, dt, ragged = self.k, self.dtype, self.shapes is not None
         if not self._h:
             raise ValueError("ManySolver: the handle is closed")
         if start not in self._STARTS:
             raise ValueError("ManySolver: start must be 'cold', 'warm' or 'last', got %r" % (start,))
-        if self.shapes is not None:
-            return self._solve_ragged(fs, gs, rho, start, x0, l0, abs_tol, rel_tol, max_iter, verbose, adaptive_rho,
-                                      gap_stop)
-        fs, gs = list(fs), list(gs)
-        if len(fs) != k or len(gs) != k:
-            raise ValueError("ManySolver: %d matrices, %d f and %d g function vectors" % (k, len(fs), len(gs)))
+        if not ragged:
+            fs, gs = _counted("ManySolver", k, fs, gs)      # (a uniform handle counts first, a ragged one after rho)
         if start == "warm":
-            if x0 is None or l0 is None:
-                raise ValueError("ManySolver: start='warm' needs both x0 (k x n) and l0 (k x m)")
-            x0 = np.ascontiguousarray(x0, dtype=dt)
-            l0 = np.ascontiguousarray(l0, dtype=dt)
-            if x0.shape != (k, n) or l0.shape != (k, m):
-                raise ValueError("ManySolver: x0 must be %d x %d and l0 %d x %d, got %s and %s"
-                                 % (k, n, k, m, x0.shape, l0.shape))
+            x0, l0 = self._starts(x0, l0)
         elif x0 is not None or l0 is not None:
             raise ValueError("ManySolver: x0 / l0 are read with start='warm' only")
-        rhos = None
-        if rho is not None:
-            rhos = np.full(k, float(rho)) if np.ndim(rho) == 0 else np.ascontiguousarray(rho, dtype=np.float64).ravel()
-            if len(rhos) != k:
-                raise ValueError("ManySolver: %d problems and %d rho values" % (k, len(rhos)))
-        keep = []
-        fa = (_lib.PogsAmdFn * k)()
-        ga = (_lib.PogsAmdFn * k)()
-        for j in range(k):
-            if len(fs[j]) != m or len(gs[j]) != n:
-                raise ValueError("ManySolver: f must have length %d and g length %d, got %d and %d"
-                                 % (m, n, len(fs[j]), len(gs[j])))
-            fa[j] = _fn_struct(fs[j], m, dt, keep)
-            ga[j] = _fn_struct(gs[j], n, dt, keep)
-        x = np.zeros((k, n), dt)
-        y = np.zeros((k, m), dt)
-        l = np.zeros((k, m), dt)
-        mu = np.zeros((k, n), dt)
-        optval = np.zeros(k, np.float64)
-        final_iter = np.zeros(k, np.uint32)
-        status = np.zeros(k, np.int32)
-        rho_final = np.zeros(k, np.float64)
+        rhos = None if rho is None else _rho_vector("ManySolver", rho, k)
+        ms, ns = ([s[0] for s in self.shapes], [s[1] for s in self.shapes]) if ragged else (self.m, self.n)
+        fa, ga, keep = _fn_arrays("ManySolver", fs, gs, self.shapes if ragged else [(ms, ns)] * k, dt, each=ragged)
+        out = _Outputs(dt, k, ms, ns, rho=True)
         st = lib.PogsAmdManySolveFn(self._h, fa, ga, None if rhos is None else _ptr(rhos), self._STARTS[start],
-                                    None if x0 is None else _ptr(x0), None if l0 is None else _ptr(l0), abs_tol,
-                                    rel_tol, int(max_iter), int(verbose), int(adaptive_rho), int(gap_stop), _ptr(x),
-                                    _ptr(y), _ptr(l), _ptr(mu), _ptr(optval), _ptr(final_iter), _ptr(status),
-                                    _ptr(rho_final))
+                                    None if x0 is None else _ptr(x0), None if l0 is None else _ptr(l0),
+                                    *_tail(abs_tol, rel_tol, max_iter, verbose, adaptive_rho, gap_stop),
+                                    *out.pointers())
         del keep
         if st != 0:
             raise RuntimeError("pogs_amd: many-problem solve failed: " + _lib.last_error())
-        return {"x": x, "y": y, "l": l, "mu": mu, "optval": optval, "iterations": final_iter.astype(np.int64),
-                "status": status.astype(np.int64), "rho": rho_final}
+        return out.arrays()
 
     def info(self):
         """k, m, n, dtype code, resident bytes, create's setup seconds and the last solve's loop seconds, launches

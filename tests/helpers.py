@@ -10,6 +10,21 @@ def soa(fv):
     return {k: getattr(fv, k) for k in "habcde"}
 
 
+def fn_arrays(fs, gs, dtype):
+    """(fa, ga, keep) for a raw call of the library: the function vectors `fs` and `gs`, each at its own length, as two
+    PogsAmdFn arrays (of one unused element where a list is empty), and the list that keeps their coefficient arrays
+    alive."""
+    from pogs_amd import _lib
+
+    keep = []
+    fa = (_lib.PogsAmdFn * max(len(fs), 1))()
+    ga = (_lib.PogsAmdFn * max(len(gs), 1))()
+    for arr, vectors in ((fa, fs), (ga, gs)):
+        for j, v in enumerate(vectors):
+            arr[j] = G._fn_struct(v, len(v), dtype, keep)
+    return fa, ga, keep
+
+
 def relerr(a, b):
     a = np.asarray(a, np.float64)
     b = np.asarray(b, np.float64)

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 import oracle_binding as ob
-from helpers import PROBLEMS, objective, relerr, soa
+from helpers import PROBLEMS, fn_arrays, objective, relerr, soa
 
 pytestmark = pytest.mark.gpu
 
@@ -174,20 +174,13 @@ def _raw_batch(s, k, fs, gs):
     """PogsAmdSolveBatchFn with k as given (no splitting): (return code, last error)."""
     from pogs_amd import _lib
 
-    kk = max(k, 1)
-    fa = (_lib.PogsAmdFn * max(len(fs), 1))()
-    ga = (_lib.PogsAmdFn * max(len(gs), 1))()
-    keep = []
-    for j in range(len(fs)):
-        (fst, gst), kp = s._coef(fs[j], gs[j])
-        fa[j], ga[j] = fst, gst
-        keep.append(kp)
+    fa, ga, keep = fn_arrays(fs, gs, s.dtype)
     x = np.zeros((max(len(fs), 1), s.n), s.dtype)
     it = np.zeros(max(len(fs), 1), np.uint32)
     st = np.zeros(max(len(fs), 1), np.int32)
     rc = _lib.lib.PogsAmdSolveBatchFn(s._h, k, fa, ga, None, 1e-4, 1e-4, 2500, 0, 1, 1, x.ctypes.data, None, None, None,
                                       None, it.ctypes.data, st.ctypes.data)
-    del keep, kk
+    del keep
     return rc, _lib.last_error()
 
 

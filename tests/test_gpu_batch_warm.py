@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 import oracle_binding as ob
-from helpers import PROBLEMS, _fsum, objective, relerr, soa
+from helpers import PROBLEMS, _fsum, fn_arrays, objective, relerr, soa
 
 pytestmark = pytest.mark.gpu
 
@@ -216,13 +216,7 @@ def _raw(s, fs, gs, rho=None, x0=None, l0=None, warm=None, want_rho=True, k=None
 
     cnt = len(fs)
     k = cnt if k is None else k
-    fa = (_lib.PogsAmdFn * max(cnt, 1))()
-    ga = (_lib.PogsAmdFn * max(cnt, 1))()
-    keep = []
-    for j in range(cnt):
-        (fst, gst), kp = s._coef(fs[j], gs[j])
-        fa[j], ga[j] = fst, gst
-        keep.append(kp)
+    fa, ga, keep = fn_arrays(fs, gs, s.dtype)
     rows = max(cnt, 1)
     out = {"x": np.full((rows, s.n), 7, s.dtype), "y": np.full((rows, s.m), 7, s.dtype),
            "l": np.full((rows, s.m), 7, s.dtype), "mu": np.full((rows, s.n), 7, s.dtype),

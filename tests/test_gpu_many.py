@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 import oracle_binding as ob
-from helpers import PROBLEMS, _fsum, objective, relerr, soa
+from helpers import PROBLEMS, _fsum, fn_arrays, objective, relerr, soa
 from pogs_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -248,16 +248,11 @@ def test_many_envelope_edge_fp32():
 def _raw_many(k, m, n, A, fs, gs, dtype_code=1, projector=1, x_null=False, it_null=False, st_null=False,
               mem=0):
     """PogsAmdSolveManyFn as given (no Python checks): (return code, last error, x, iterations, status)."""
-    from pogs_amd import _lib, graph
+    from pogs_amd import _lib
 
-    keep = []
     cnt = max(len(fs), 1)
-    fa = (_lib.PogsAmdFn * cnt)()
-    ga = (_lib.PogsAmdFn * cnt)()
     dt = np.float64 if dtype_code == 1 else np.float32
-    for j in range(len(fs)):
-        fa[j] = graph._fn_struct(fs[j], len(fs[j]), dt, keep)
-        ga[j] = graph._fn_struct(gs[j], len(gs[j]), dt, keep)
+    fa, ga, keep = fn_arrays(fs, gs, dt)
     x = np.full((cnt, max(n, 1)), 7.0, dt)
     it = np.full(cnt, 77, np.uint32)
     st = np.full(cnt, 55, np.int32)

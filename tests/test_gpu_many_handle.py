@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 import oracle_binding as ob
-from helpers import PROBLEMS, _fsum, objective, relerr, soa
+from helpers import PROBLEMS, _fsum, fn_arrays, objective, relerr, soa
 
 pytestmark = pytest.mark.gpu
 
@@ -362,15 +362,10 @@ def test_the_handle_owns_its_copy_of_a_device_tensor(dtype, colmajor):
 
 def _raw_solve(s, fs, gs, start, x0=None, l0=None, x_null=False, it_null=False, st_null=False, f_null=False):
     """PogsAmdManySolveFn as given (no Python checks) with sentinel-filled outputs: (return code, last error, outputs)."""
-    from pogs_amd import _lib, graph
+    from pogs_amd import _lib
 
-    keep = []
     k, m, n, dt = s.k, s.m, s.n, s.dtype
-    fa = (_lib.PogsAmdFn * k)()
-    ga = (_lib.PogsAmdFn * k)()
-    for j in range(k):
-        fa[j] = graph._fn_struct(fs[j], m, dt, keep)
-        ga[j] = graph._fn_struct(gs[j], n, dt, keep)
+    fa, ga, keep = fn_arrays(fs, gs, dt)
     out = dict(x=np.full((k, n), 7.0, dt), y=np.full((k, m), 7.0, dt), l=np.full((k, m), 7.0, dt),
                mu=np.full((k, n), 7.0, dt), optval=np.full(k, 7.0), it=np.full(k, 77, np.uint32),
                st=np.full(k, 55, np.int32), rho=np.full(k, 7.0))

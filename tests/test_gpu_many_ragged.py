@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 import oracle_binding as ob
-from helpers import PROBLEMS, _fsum, objective, relerr, soa
+from helpers import PROBLEMS, _fsum, fn_arrays, objective, relerr, soa
 
 pytestmark = pytest.mark.gpu
 
@@ -337,15 +337,10 @@ def test_handle_shapes_and_info():
 
 def _raw_handle_solve(s, fs, gs, start, x_null=False):
     """PogsAmdManySolveFn on the handle of `s` as given: (return code, last error, x, iterations, status)."""
-    from pogs_amd import _lib, graph
+    from pogs_amd import _lib
 
-    keep = []
     k = s.k
-    fa = (_lib.PogsAmdFn * k)()
-    ga = (_lib.PogsAmdFn * k)()
-    for j in range(k):
-        fa[j] = graph._fn_struct(fs[j], len(fs[j]), s.dtype, keep)
-        ga[j] = graph._fn_struct(gs[j], len(gs[j]), s.dtype, keep)
+    fa, ga, keep = fn_arrays(fs, gs, s.dtype)
     x = np.full(sum(n for _, n in s.shapes), 7.0, s.dtype)
     y = np.full(sum(m for m, _ in s.shapes), 7.0, s.dtype)
     it = np.full(k, 77, np.uint32)

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 import oracle_binding as ob
-from helpers import PROBLEMS, relerr, soa
+from helpers import PROBLEMS, fn_arrays, relerr, soa
 from test_gpu_batch import _check as _dense_check
 from test_gpu_batch import _same_bytes, _xtol32
 
@@ -230,13 +230,7 @@ def _raw_batch(s, k, fs, gs):
     """PogsAmdSolveBatchSparseFn with k as given (no splitting): (return code, last error)."""
     from pogs_amd import _lib
 
-    fa = (_lib.PogsAmdFn * max(len(fs), 1))()
-    ga = (_lib.PogsAmdFn * max(len(gs), 1))()
-    keep = []
-    for j in range(len(fs)):
-        (fst, gst), kp = s._coef(fs[j], gs[j])
-        fa[j], ga[j] = fst, gst
-        keep.append(kp)
+    fa, ga, keep = fn_arrays(fs, gs, s.dtype)
     x = np.zeros((max(len(fs), 1), s.n), s.dtype)
     it = np.zeros(max(len(fs), 1), np.uint32)
     st = np.zeros(max(len(fs), 1), np.int32)

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import pogs_amd
+from helpers import fn_arrays
 from pogs_amd import _lib, graph
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
@@ -135,15 +136,10 @@ def test_solve_many_with_unequal_matrices_still_raises(no_library):
 def _raw_ragged(k, ms, ns, A="own", fs="own", gs="own", dtype_code=1, ord_code=1, projector=1, m_null=False,
                 n_null=False, x_null=False, it_null=False, st_null=False):
     """PogsAmdSolveManyRaggedFn as given (no Python checks): (return code, last error, x, iterations, status)."""
-    keep = []
     cnt = max(len(ms), 1)
     dt = np.float64 if dtype_code == 1 else np.float32
-    fa = (_lib.PogsAmdFn * cnt)()
-    ga = (_lib.PogsAmdFn * cnt)()
-    for j in range(len(ms)):
-        f, g = graph.lasso_functions(np.ones(3), 0.1, 3)     # broadcast-free, tiny: never read by a refused call
-        fa[j] = graph._fn_struct(f, 3, dt, keep)
-        ga[j] = graph._fn_struct(g, 3, dt, keep)
+    fgs = [graph.lasso_functions(np.ones(3), 0.1, 3) for _ in ms]     # tiny: never read by a refused call
+    fa, ga, keep = fn_arrays([p[0] for p in fgs], [p[1] for p in fgs], dt)
     Abuf = np.ones(64, dt)
     x = np.full(64, 7.0, dt)
     it = np.full(cnt, 77, np.uint32)
