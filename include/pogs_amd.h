@@ -212,7 +212,9 @@ int PogsAmdDistUniqueId(char *out);
  * missed rho prediction, the exact-residual pass of the lean form, PogsAmdMul, PogsAmdProject, the batch entries --
  * reads the fp64 copy with its existing kernel.  Both copies hold the same numbers, so only the order of some sums
  * differs.  POGS_AMD_MIXED_PASS=0 in the environment, read at create, keeps the rounding and both copies but runs
- * every pass on the fp64 copy (the A / B leg of a measurement).
+ * every pass on the fp64 copy (the A / B leg of a measurement).  (The multi-vector kernels that would let the batch
+ * entries read the float copy exist and are tested on their own -- PogsAmdBatchRowsMixedCheck below -- but the batch
+ * entries do not call them yet.)
  * Honoured for: dtype F64, m > n, projector DEFAULT or DIRECT, no dist, n <= 10240 (the row fits a one-pass shape of
  * the mixed plan: not windowed and no wider than the fp64 one-pass iteration reaches).  Refused before anything is
  * built -- POGS_ERROR, *out NULL, PogsAmdLastError names the reason: dtype F32, m <= n, either CGLS value, row shards,
@@ -577,6 +579,18 @@ int PogsAmdBatchRowsCheck(int dtype, int tri, int rows, int cols, const void *M,
  * ldz >= cols_pad (also add's).  *nrb_used and *rpb report the partition: row blocks and rows per block. */
 int PogsAmdBatchColsCheck(int dtype, int rows, int cols, const void *M, size_t ldm, int k, const int *act, int nact,
                           const void *U, size_t ldu, const void *add, void *Z, size_t ldz, int *nrb_used, int *rpb);
+/* The two entries above for a matrix stored as floats -- the kernels with which a batched solve on a mixed-storage
+ * handle (POGS_AMD_STORE_F32) can read the float copy (launch_batch_rows_mixed, launch_batch_cols_mixed over the fp64
+ * row-block partition, then launch_batch_cols_reduce): dtype fp64 is implied and the full form only.  M is a HOST
+ * array of FLOATS, rows x ldm row-major, ldm a multiple of 4 and >= round_up(cols, 4); X / U / Y / Z / add are doubles
+ * under the fp64 entries' constraints (ldx, ldz multiples of 2 and >= round_up(cols, 2); ldy, ldu >= rows).  The
+ * results are, bit for bit, those of the fp64 entries on M widened to doubles, *nrb_used and *rpb included; what M
+ * holds from column cols to ldm is never used (tests/test_gpu_batch_mixed_kernels.py). */
+int PogsAmdBatchRowsMixedCheck(int rows, int cols, const float *M, size_t ldm, int k, const int *act, int nact,
+                               const double *X, size_t ldx, double *Y, size_t ldy);
+int PogsAmdBatchColsMixedCheck(int rows, int cols, const float *M, size_t ldm, int k, const int *act, int nact,
+                               const double *U, size_t ldu, const double *add, double *Z, size_t ldz, int *nrb_used,
+                               int *rpb);
 /* Y[p][r] = sum_q val[q] X[p][ind[q]] over ptr[r] <= q < ptr[r+1] (+ beta yin[p][r] when yin is not NULL), the
  * batched sparse solve's product (sp_batch_geometry, launch_sp_batch_pack, launch_sp_batch_spmv).  CSR of
  * nrows x ncols: ptr (nrows + 1, ptr[0] == 0, non-decreasing), ind in [0, ncols) (int32).  ldx >= ncols,

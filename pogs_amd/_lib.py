@@ -198,6 +198,10 @@ lib.PogsAmdBatchRowsCheck.argtypes = [c_int, c_int, c_int, c_int, c_void_p, c_si
 lib.PogsAmdBatchColsCheck.argtypes = [c_int, c_int, c_int, c_void_p, c_size_t, c_int, c_void_p, c_int, c_void_p,
                                       c_size_t, c_void_p, c_void_p, c_size_t, ctypes.POINTER(c_int),
                                       ctypes.POINTER(c_int)]
+lib.PogsAmdBatchRowsMixedCheck.argtypes = [c_int, c_int, c_void_p, c_size_t, c_int, c_void_p, c_int, c_void_p, c_size_t,
+                                           c_void_p, c_size_t]
+lib.PogsAmdBatchColsMixedCheck.argtypes = [c_int, c_int, c_void_p, c_size_t, c_int, c_void_p, c_int, c_void_p, c_size_t,
+                                           c_void_p, c_void_p, c_size_t, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]
 lib.PogsAmdSpBatchSpmvCheck.argtypes = [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
                                         c_void_p, c_size_t, c_double, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p,
                                         c_int, c_void_p]
@@ -273,7 +277,7 @@ ABI_SYMBOLS = [
     "PogsAmdSpBatchSpmvCheck", "PogsAmdManySetupCheck", "PogsAmdGramCheck", "PogsAmdCholCheck",
     "PogsAmdSpmvCheck", "PogsAmdSparseCgCheck", "PogsAmdGetFactor", "PogsAmdSparseGramCheck", "PogsAmdTriMatvecCheck",
     "PogsAmdDensePassCheck", "PogsAmdDenseCgCheck", "PogsAmdVecCheck", "PogsAmdDensePassMixedCheck",
-    "PogsAmdCreateSparseMixed", "PogsAmdSpmvMixedCheck",
+    "PogsAmdCreateSparseMixed", "PogsAmdSpmvMixedCheck", "PogsAmdBatchRowsMixedCheck", "PogsAmdBatchColsMixedCheck",
 ]
 
 
@@ -354,6 +358,49 @@ def batch_cols_check(M, cols, U, Z, act, add=None):
     if lib.PogsAmdBatchColsCheck(code, M.shape[0], cols, M.ctypes.data, M.shape[1], U.shape[0], a.ctypes.data, a.size,
                                  U.ctypes.data, U.shape[1], None if add is None else arrays[3].ctypes.data,
                                  Z.ctypes.data, Z.shape[1], ctypes.byref(nrb), ctypes.byref(rpb)) != 0:
+        raise RuntimeError(last_error())
+    return Z, nrb.value, rpb.value
+
+
+def _mixed_arrays(M, *doubles):
+    import numpy as np
+    M = np.ascontiguousarray(M)
+    doubles = [np.ascontiguousarray(a) for a in doubles]
+    if M.dtype != np.float32 or any(a.dtype != np.float64 for a in doubles):
+        raise ValueError("M float32, every other array float64")
+    return [M] + doubles
+
+
+def batch_rows_mixed_check(M, cols, X, Y, act):
+    """batch_rows_check (full form) by the batched row-dot kernel for a matrix stored as float32
+    (include/pogs_amd.h: PogsAmdBatchRowsMixedCheck).  M: rows x ldm float32; X: k x ldx, Y: k x ldy float64.
+    Returns a new array; Y itself is not changed."""
+    import numpy as np
+    M, X, Y = _mixed_arrays(M, X, np.array(Y, order="C", copy=True))
+    if M.ndim != 2 or X.ndim != 2 or Y.ndim != 2 or X.shape[0] != Y.shape[0]:
+        raise ValueError("M (rows, ldm), X (k, ldx), Y (k, ldy)")
+    a = _act(act)
+    if lib.PogsAmdBatchRowsMixedCheck(M.shape[0], cols, M.ctypes.data, M.shape[1], X.shape[0], a.ctypes.data, a.size,
+                                      X.ctypes.data, X.shape[1], Y.ctypes.data, Y.shape[1]) != 0:
+        raise RuntimeError(last_error())
+    return Y
+
+
+def batch_cols_mixed_check(M, cols, U, Z, act, add=None):
+    """batch_cols_check by the batched column-sum kernels for a matrix stored as float32 (include/pogs_amd.h:
+    PogsAmdBatchColsMixedCheck): (Z, nrb_used, rpb).  M: rows x ldm float32; U: k x ldu, Z and add: k x ldz float64.
+    Returns a new array; Z itself is not changed."""
+    import numpy as np
+    arrays = _mixed_arrays(M, U, np.array(Z, order="C", copy=True), *(() if add is None else (add,)))
+    M, U, Z = arrays[:3]
+    if M.ndim != 2 or U.ndim != 2 or Z.ndim != 2 or U.shape[0] != Z.shape[0] or \
+            (add is not None and arrays[3].shape != Z.shape):
+        raise ValueError("M (rows, ldm), U (k, ldu), Z and add (k, ldz)")
+    a = _act(act)
+    nrb, rpb = c_int(0), c_int(0)
+    if lib.PogsAmdBatchColsMixedCheck(M.shape[0], cols, M.ctypes.data, M.shape[1], U.shape[0], a.ctypes.data, a.size,
+                                      U.ctypes.data, U.shape[1], None if add is None else arrays[3].ctypes.data,
+                                      Z.ctypes.data, Z.shape[1], ctypes.byref(nrb), ctypes.byref(rpb)) != 0:
         raise RuntimeError(last_error())
     return Z, nrb.value, rpb.value
 

@@ -843,6 +843,23 @@ int PogsAmdBatchColsCheck(int dtype, int rows, int cols, const void *M, size_t l
   });
 }
 
+int PogsAmdBatchRowsMixedCheck(int rows, int cols, const float *M, size_t ldm, int k, const int *act, int nact,
+                               const double *X, size_t ldx, double *Y, size_t ldy) {
+  return guarded([&]() {
+    batch_rows_mixed_check(rows, cols, M, ldm, k, act, nact, X, ldx, Y, ldy);
+    return 0;
+  });
+}
+
+int PogsAmdBatchColsMixedCheck(int rows, int cols, const float *M, size_t ldm, int k, const int *act, int nact,
+                               const double *U, size_t ldu, const double *add, double *Z, size_t ldz, int *nrb_used,
+                               int *rpb) {
+  return guarded([&]() {
+    batch_cols_mixed_check(rows, cols, M, ldm, k, act, nact, U, ldu, add, Z, ldz, nrb_used, rpb);
+    return 0;
+  });
+}
+
 int PogsAmdSpBatchSpmvCheck(int dtype, int nrows, int ncols, const int *ptr, const int *ind, const void *val, int k,
                             const int *act, int nact, const void *X, size_t ldx, double beta, const void *yin,
                             size_t ldin, void *Y, size_t ldy, double *part, int num_cu, int *geom) {

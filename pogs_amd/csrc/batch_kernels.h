@@ -75,6 +75,16 @@ inline void batch_cols_partition(int rows, int cols_pad, int &rpb, int &nrb_used
 template <typename T>
 void launch_batch_cols_reduce(const T *part, int nrb, int kb, int cols, int cols_pad, const T *add, T *Z, size_t ldz,
                               const BatchSlots &sl, hipStream_t s);
+// Mixed storage (DenseSolver's float copy of A, stream_mixed.h): launch_batch_rows<double>(kFull, ...) and
+// launch_batch_cols<double> over a matrix stored as floats, rows of round_up(cols, 4) floats at stride ldm (a multiple
+// of 4).  Vectors, partials and arithmetic are fp64, cols_pad = round_up(cols, 2), and the row-block partition is
+// batch_cols_partition<double>'s: the results are, bit for bit, those of the fp64 launches on the widened matrix
+// (launch_batch_cols_reduce<double> is the second stage of both).
+constexpr int kBatchColsMixedSlab = 64;   // columns per slab of launch_batch_cols_mixed
+void launch_batch_rows_mixed(const float *M, size_t ldm, int rows, int cols, int cols_pad, const double *X, size_t ldx,
+                             double *Y, size_t ldy, const BatchSlots &sl, hipStream_t s);
+void launch_batch_cols_mixed(const float *M, size_t ldm, int rows, int cols_pad, int rows_per_block, int nrb,
+                             const double *U, size_t ldu, double *part, int kb, const BatchSlots &sl, hipStream_t s);
 // element-wise stages over x blocks (vec_blocks(n)) and y blocks (vec_blocks(m)), one grid row per slot
 template <typename T> void launch_batch_pre(const BatchVecArgs<T> &a, hipStream_t s);
 template <typename T> void launch_batch_tail(const BatchVecArgs<T> &a, hipStream_t s);
@@ -124,5 +134,11 @@ void batch_rows_check(int tri, int rows, int cols, const T *M, size_t ldm, int k
 template <typename T>
 void batch_cols_check(int rows, int cols, const T *M, size_t ldm, int k, const int *act, int nact, const T *U,
                       size_t ldu, const T *add, T *Z, size_t ldz, int *nrb_used, int *rpb);
+// Behind PogsAmdBatchRowsMixedCheck / PogsAmdBatchColsMixedCheck: the same for the mixed launches (M: floats).
+void batch_rows_mixed_check(int rows, int cols, const float *M, size_t ldm, int k, const int *act, int nact,
+                            const double *X, size_t ldx, double *Y, size_t ldy);
+void batch_cols_mixed_check(int rows, int cols, const float *M, size_t ldm, int k, const int *act, int nact,
+                            const double *U, size_t ldu, const double *add, double *Z, size_t ldz, int *nrb_used,
+                            int *rpb);
 
 }  // namespace pogs_amd

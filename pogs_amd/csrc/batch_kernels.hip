@@ -185,6 +185,162 @@ __global__ void __launch_bounds__(256) batch_cols_reduce_kernel(const T *__restr
   Z[static_cast<size_t>(p) * ldz + col] = col < cols ? v : static_cast<T>(0);
 }
 
+// ---- mixed storage: the two passes over A on a float copy of the matrix, fp64 vectors and arithmetic ---------------
+// batch_rows_kernel<double, kFull> and batch_cols_kernel<double> with the matrix operand stored as floats
+// (DenseSolver's A32_, stream_mixed.h): 4 instead of 8 bytes per entry, each float widened where it is used (exact).
+// Every output element is added up in the fp64 kernel's order -- the same columns in the same (wave, step, MFMA, k)
+// places, the same rows in the same (wave, step, quad, k) places -- so the result is, bit for bit, what the fp64
+// kernel returns for the widened matrix.  Loads are unconditional on addresses clamped into the matrix, masks are
+// applied afterwards (stream_mixed.h: a guarded load is a branch, and behind it every load is waited for on its own).
+
+__device__ __forceinline__ float2 stream_load_f2(const float *p) {
+#if POGS_AMD_NT_LOADS
+  typedef unsigned int raw8 __attribute__((ext_vector_type(2)));
+  const raw8 raw = __builtin_nontemporal_load(reinterpret_cast<const raw8 *>(p));
+  float2 out;
+  __builtin_memcpy(&out, &raw, 8);
+  return out;
+#else
+  return *reinterpret_cast<const float2 *>(p);
+#endif
+}
+
+// Row dots.  The fp64 geometry (VEC = 2, STEP = 8) with 8-byte loads: lane l loads the two floats of row (l & 15) at
+// column c0 + 2 (l >> 4), which are the two doubles the fp64 kernel's lane loads -- the mapping of columns to
+// (wave, step, MFMA, k) needs no further work.  Whatever the float row holds from cols on is masked.
+__global__ void __launch_bounds__(256) batch_rows_mixed_kernel(const float *__restrict__ M, size_t ldm, int rows,
+                                                               int cols, int cols_pad, const double *__restrict__ X,
+                                                               size_t ldx, double *__restrict__ Y, size_t ldy,
+                                                               BatchSlots sl) {
+  using MF = BatchMfma<double>;
+  constexpr int VEC = Vec16<double>::N;
+  constexpr int STEP = 4 * VEC;
+  __shared__ double red[4][kBRowsPerWg][17];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int i = lane & 15, q = lane >> 4;
+  const int r0 = blockIdx.x * kBRowsPerWg;
+  const bool vec_on = i < sl.nact;
+  const double *xp = X + (vec_on ? static_cast<size_t>(sl.act[i]) * ldx : 0);
+  const float *rp[kBRowGroups];
+  bool row_in[kBRowGroups];
+  MF::acc acc[kBRowGroups];
+#pragma unroll
+  for (int g = 0; g < kBRowGroups; ++g) {
+    const int row = r0 + 16 * g + i;
+    row_in[g] = row < rows;
+    rp[g] = M + static_cast<size_t>(row_in[g] ? row : rows - 1) * ldm;
+    acc[g] = MF::acc{0, 0, 0, 0};
+  }
+  struct Tile {
+    float2 a[kBRowGroups];
+    double2 x;
+  };
+  // (unconditional: a lane past the row's end reads column 0 again and is masked in `use`)
+  auto load = [&](int cb, Tile &t) {
+    const int c = cb + VEC * q;
+    const int cc = c < cols_pad ? c : 0;   // (cc + 1 < cols_pad <= min(ldx, ldm))
+    t.x = *reinterpret_cast<const double2 *>(xp + cc);
+#pragma unroll
+    for (int g = 0; g < kBRowGroups; ++g) t.a[g] = stream_load_f2(rp[g] + cc);
+  };
+  auto use = [&](int cb, const Tile &t) {
+    const int c = cb + VEC * q;
+    const bool x_on = vec_on && c < cols_pad;
+    const double xe[VEC] = {x_on ? t.x.x : 0.0, x_on ? t.x.y : 0.0};
+#pragma unroll
+    for (int g = 0; g < kBRowGroups; ++g) {
+      const float ae[VEC] = {t.a[g].x, t.a[g].y};
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) {
+        const bool keep = row_in[g] && c + k < cols;
+        acc[g] = MF::mfma(keep ? static_cast<double>(ae[k]) : 0.0, xe[k], acc[g]);
+      }
+    }
+  };
+  // (the wave index as a scalar: the loop's control is then the scalar unit's)
+  for (int cb = __builtin_amdgcn_readfirstlane(w) * STEP; cb < cols; cb += 4 * STEP) {
+    Tile t;
+    load(cb, t);
+    use(cb, t);
+  }
+#pragma unroll
+  for (int g = 0; g < kBRowGroups; ++g)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) red[w][16 * g + MF::row(lane, r)][i] = acc[g][r];
+  __syncthreads();
+  for (int o = threadIdx.x; o < kBRowsPerWg * 16; o += 256) {
+    const int rr = o >> 4, j = o & 15;
+    const int row = r0 + rr;
+    if (j < sl.nact && row < rows) {
+      const double v = ((red[0][rr][j] + red[1][rr][j]) + red[2][rr][j]) + red[3][rr][j];
+      Y[static_cast<size_t>(sl.act[j]) * ldy + row] = v;
+    }
+  }
+}
+
+// Column sums, first stage.  A column's chain runs over rows only, so the slab width is free: 16-byte loads of four
+// floats over a slab of 64 columns, four accumulators; rows are dealt as in batch_cols_kernel<double> (wave w takes the
+// quads rlo + 4 w + 64 s, four quads per step, k = the row within the quad).  cols_pad = round_up(cols, 2) is the
+// length of a partials record; the float row runs to round_up(cols, 4) <= ldm, so the last vector of a row may cover
+// two columns with no slot (cols_pad % 4 == 2): they are loaded and summed, and never stored.
+__global__ void __launch_bounds__(256) batch_cols_mixed_kernel(const float *__restrict__ M, size_t ldm, int rows,
+                                                               int cols_pad, int rows_per_block,
+                                                               const double *__restrict__ U, size_t ldu,
+                                                               double *__restrict__ part, int kb, BatchSlots sl) {
+  using MF = BatchMfma<double>;
+  constexpr int VEC = 4;
+  constexpr int SLAB = kBatchColsMixedSlab;
+  constexpr int QU = 4;
+  static_assert(SLAB == 16 * VEC, "slab width");
+  __shared__ double red[4][SLAB][17];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int i = lane & 15, k = lane >> 4;
+  const int cs = blockIdx.x * SLAB;
+  const int rb = blockIdx.y;
+  const int rlo = rb * rows_per_block, rhi = min(rows, rlo + rows_per_block);
+  const bool vec_on = i < sl.nact;
+  const double *up = U + (vec_on ? static_cast<size_t>(sl.act[i]) * ldu : 0);
+  const int c = cs + VEC * i;
+  const bool col_in = c < cols_pad;
+  const float *cp = M + (col_in ? c : 0);   // (c + 3 < round_up(cols_pad, 4) <= ldm)
+  MF::acc acc[VEC];
+#pragma unroll
+  for (int t = 0; t < VEC; ++t) acc[t] = MF::acc{0, 0, 0, 0};
+  for (int rq = rlo + 4 * w; rq < rhi; rq += 16 * QU) {
+    float4 av[QU];
+    double uv[QU];
+#pragma unroll
+    for (int u = 0; u < QU; ++u) {
+      const int row = rq + 16 * u + k;
+      const int rc = row < rhi ? row : rhi - 1;
+      av[u] = stream_load<float4>(cp + static_cast<size_t>(rc) * ldm);
+      uv[u] = up[rc];
+    }
+#pragma unroll
+    for (int u = 0; u < QU; ++u) {
+      const int row = rq + 16 * u + k;
+      const bool a_on = row < rhi && col_in;
+      const double ub = (row < rhi && vec_on) ? uv[u] : 0.0;
+      const float ae[VEC] = {av[u].x, av[u].y, av[u].z, av[u].w};
+#pragma unroll
+      for (int t = 0; t < VEC; ++t) acc[t] = MF::mfma(a_on ? static_cast<double>(ae[t]) : 0.0, ub, acc[t]);
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < VEC; ++t)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) red[w][VEC * MF::row(lane, r) + t][i] = acc[t][r];
+  __syncthreads();
+  for (int o = threadIdx.x; o < SLAB * 16; o += 256) {
+    const int cc = o >> 4, j = o & 15;
+    const int col = cs + cc;
+    if (j < sl.nact && col < cols_pad) {
+      const double v = ((red[0][cc][j] + red[1][cc][j]) + red[2][cc][j]) + red[3][cc][j];
+      part[(static_cast<size_t>(rb) * kb + sl.act[j]) * cols_pad + col] = v;
+    }
+  }
+}
+
 // ---- element-wise stages, blockIdx.y = slot; x blocks first, then y blocks ---------------------------------------
 // prox + over-relaxation (pogs.cpp:257-278; admm_pre_kernel), sums {w h, w^2, h^2}
 template <typename T>
@@ -359,6 +515,18 @@ void launch_batch_cols_reduce(const T *part, int nrb, int kb, int cols, int cols
                      cols, cols_pad, add, Z, ldz, sl);
 }
 
+void launch_batch_rows_mixed(const float *M, size_t ldm, int rows, int cols, int cols_pad, const double *X, size_t ldx,
+                             double *Y, size_t ldy, const BatchSlots &sl, hipStream_t s) {
+  hipLaunchKernelGGL(batch_rows_mixed_kernel, dim3((rows + kBRowsPerWg - 1) / kBRowsPerWg), dim3(256), 0, s, M, ldm,
+                     rows, cols, cols_pad, X, ldx, Y, ldy, sl);
+}
+
+void launch_batch_cols_mixed(const float *M, size_t ldm, int rows, int cols_pad, int rows_per_block, int nrb,
+                             const double *U, size_t ldu, double *part, int kb, const BatchSlots &sl, hipStream_t s) {
+  hipLaunchKernelGGL(batch_cols_mixed_kernel, dim3((cols_pad + kBatchColsMixedSlab - 1) / kBatchColsMixedSlab, nrb),
+                     dim3(256), 0, s, M, ldm, rows, cols_pad, rows_per_block, U, ldu, part, kb, sl);
+}
+
 template <typename T>
 void launch_batch_pre(const BatchVecArgs<T> &a, hipStream_t s) {
   hipLaunchKernelGGL(batch_pre_kernel<T>, dim3(a.bx + a.by, a.sl.nact), dim3(kVecTpb), 0, s, a);
@@ -435,6 +603,60 @@ void batch_cols_check(int rows, int cols, const T *M, size_t ldm, int k, const i
                               nullptr);
   POGS_HIP_CHECK(hipGetLastError());
   POGS_HIP_CHECK(hipMemcpy(Z, dZ.p, nz * sizeof(T), hipMemcpyDeviceToHost));
+  POGS_HIP_CHECK(hipDeviceSynchronize());
+  *nrb_used = nrb;
+  *rpb = rb;
+}
+
+void batch_rows_mixed_check(int rows, int cols, const float *M, size_t ldm, int k, const int *act, int nact,
+                            const double *X, size_t ldx, double *Y, size_t ldy) {
+  const BatchSlots sl = checked_batch_slots(k, act, nact);
+  POGS_CHECK(rows >= 1 && cols >= 1, "rows and cols must be >= 1");
+  POGS_CHECK(M && X && Y, "null argument");
+  const size_t cols_pad = round_up(static_cast<size_t>(cols), 2);
+  POGS_CHECK(ldm >= round_up(static_cast<size_t>(cols), 4) && ldm % 4 == 0,
+             "ldm must be a multiple of 4 and >= round_up(cols, 4)");
+  POGS_CHECK(ldx >= cols_pad && ldx % 2 == 0, "ldx must be a multiple of 2 and >= round_up(cols, 2)");
+  POGS_CHECK(ldy >= static_cast<size_t>(rows), "ldy must be >= rows");
+  const size_t nm = static_cast<size_t>(rows) * ldm, nx = static_cast<size_t>(k) * ldx;
+  const size_t ny = static_cast<size_t>(k) * ldy;
+  DevBuf<float> dM(nm);
+  DevBuf<double> dX(nx), dY(ny);
+  POGS_HIP_CHECK(hipMemcpy(dM.p, M, nm * sizeof(float), hipMemcpyHostToDevice));
+  POGS_HIP_CHECK(hipMemcpy(dX.p, X, nx * sizeof(double), hipMemcpyHostToDevice));
+  POGS_HIP_CHECK(hipMemcpy(dY.p, Y, ny * sizeof(double), hipMemcpyHostToDevice));
+  launch_batch_rows_mixed(dM.p, ldm, rows, cols, static_cast<int>(cols_pad), dX.p, ldx, dY.p, ldy, sl, nullptr);
+  POGS_HIP_CHECK(hipGetLastError());
+  POGS_HIP_CHECK(hipMemcpy(Y, dY.p, ny * sizeof(double), hipMemcpyDeviceToHost));
+  POGS_HIP_CHECK(hipDeviceSynchronize());
+}
+
+void batch_cols_mixed_check(int rows, int cols, const float *M, size_t ldm, int k, const int *act, int nact,
+                            const double *U, size_t ldu, const double *add, double *Z, size_t ldz, int *nrb_used,
+                            int *rpb) {
+  const BatchSlots sl = checked_batch_slots(k, act, nact);
+  POGS_CHECK(rows >= 1 && cols >= 1, "rows and cols must be >= 1");
+  POGS_CHECK(M && U && Z && nrb_used && rpb, "null argument");
+  const size_t cols_pad = round_up(static_cast<size_t>(cols), 2);
+  POGS_CHECK(ldm >= round_up(static_cast<size_t>(cols), 4) && ldm % 4 == 0,
+             "ldm must be a multiple of 4 and >= round_up(cols, 4)");
+  POGS_CHECK(ldu >= static_cast<size_t>(rows), "ldu must be >= rows");
+  POGS_CHECK(ldz >= cols_pad && ldz % 2 == 0, "ldz must be a multiple of 2 and >= round_up(cols, 2)");
+  int rb = 0, nrb = 0;
+  batch_cols_partition<double>(rows, static_cast<int>(cols_pad), rb, nrb);
+  const size_t nm = static_cast<size_t>(rows) * ldm, nu = static_cast<size_t>(k) * ldu;
+  const size_t nz = static_cast<size_t>(k) * ldz;
+  DevBuf<float> dM(nm);
+  DevBuf<double> dU(nu), dZ(nz), dA(add ? nz : 0), part(static_cast<size_t>(nrb) * k * cols_pad);
+  POGS_HIP_CHECK(hipMemcpy(dM.p, M, nm * sizeof(float), hipMemcpyHostToDevice));
+  POGS_HIP_CHECK(hipMemcpy(dU.p, U, nu * sizeof(double), hipMemcpyHostToDevice));
+  POGS_HIP_CHECK(hipMemcpy(dZ.p, Z, nz * sizeof(double), hipMemcpyHostToDevice));
+  if (add) POGS_HIP_CHECK(hipMemcpy(dA.p, add, nz * sizeof(double), hipMemcpyHostToDevice));
+  launch_batch_cols_mixed(dM.p, ldm, rows, static_cast<int>(cols_pad), rb, nrb, dU.p, ldu, part.p, k, sl, nullptr);
+  launch_batch_cols_reduce<double>(part.p, nrb, k, cols, static_cast<int>(cols_pad), add ? dA.p : nullptr, dZ.p, ldz,
+                                   sl, nullptr);
+  POGS_HIP_CHECK(hipGetLastError());
+  POGS_HIP_CHECK(hipMemcpy(Z, dZ.p, nz * sizeof(double), hipMemcpyDeviceToHost));
   POGS_HIP_CHECK(hipDeviceSynchronize());
   *nrb_used = nrb;
   *rpb = rb;
