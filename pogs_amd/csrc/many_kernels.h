@@ -1,5 +1,8 @@
 // Many small dense problems, each with its own matrix (PogsAmdSolveManyFn, include/pogs_amd.h): the host driver's
-// entry.  The kernels and the driver live in many_kernels.hip; DESIGN.md section 3.7 describes the design.
+// entries.  One translation unit, many_kernels.hip, holds the driver: ManySet<T>, the device buffers of a set of
+// resident problems (one per one-shot solve, sized to its largest chunk; one per handle, for all k), the staging of A
+// and the launch sequences.  It includes many_device.h (the kernels and their argument structs) and many_plan.h (the
+// arithmetic on shapes: workspace layout, prefix sums, chunks; plain C++).  DESIGN.md section 3.7 describes the design.
 #pragma once
 #include <vector>
 
