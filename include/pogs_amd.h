@@ -269,6 +269,31 @@ int PogsAmdCreateSparseMixed(PogsAmdSolver **out, enum ORD ord, size_t m, size_t
                              const double *data, const int *ptr, const int *ind, int mem,
                              const PogsAmdOptions *opt);
 
+/* Create a MIXED-STORAGE dense solver with the one-pass CGLS projector: an fp64 POGS_AMD_PROJ_CGLS_FUSED handle over a
+ * float copy of the matrix (one GPU, no row shards, any m, tall or wide, 1 <= n <= 10240: the row fits a one-pass shape
+ * of the mixed plan, not windowed).  The arguments are those of PogsAmdCreateDense with dtype POGS_AMD_F64 implied and
+ * no dist.  opt is required: opt->projector must be POGS_AMD_PROJ_CGLS_FUSED and the storage field 0 or
+ * POGS_AMD_STORE_F32 (both mean the float copy here).  PogsAmdCreateDense itself keeps refusing POGS_AMD_STORE_F32 with
+ * either CGLS value and with m <= n: the capability lives in this entry.
+ * The equilibrated matrix is rounded to float once, at the end of the equilibration and before the norm estimate, by
+ * the code a POGS_AMD_STORE_F32 handle of PogsAmdCreateDense runs -- call it A^ -- and EVERYTHING after that is defined
+ * on A^: the norm estimate, every product, the CG loop, the residuals, the epilogue, PogsAmdGetEquil, PogsAmdMul and
+ * PogsAmdProject.  It is not an approximate projector on the unrounded matrix.  Both copies are kept (1.5 x the matrix).
+ * The RECURRING launches of the projector read the float copy, 4 bytes per entry instead of 8: u = A^T r at the start
+ * of every projection, the one pass of every CG step (q = A p with the column sums of A^T q), and the product y = A x
+ * of every POGS_AMD_YSYNC-th projection.  Every other pass -- set-up, warm start, the exact-residual pass, PogsAmdMul,
+ * the two set-up products of PogsAmdProject -- keeps its fp64 kernel on the fp64 copy; both hold the same numbers, so
+ * only the order of some sums differs.  stats: matvecs and cg_iters count as on a plain CGLS_FUSED handle; with
+ * profiling on, stream_bytes counts a launch over the float copy as m n 4.  POGS_AMD_MIXED_PASS=0 in the environment,
+ * read at create, keeps the rounding and both copies and runs every pass on the fp64 copy (the A / B leg).
+ * Refused before anything is built and with no device needed -- POGS_ERROR, *out NULL, PogsAmdLastError names the
+ * reason: a NULL argument (out, A, opt), an unknown ord or mem, bad dimensions, any projector but CGLS_FUSED,
+ * n > 10240 or a windowed row, a storage field other than 0 or POGS_AMD_STORE_F32.
+ * Every entry that takes a dense CGLS_FUSED handle works on the result, PogsAmdDenseCgCheck included; the batch entries
+ * and PogsAmdGetFactor refuse as on any CGLS handle. */
+int PogsAmdCreateDenseMixed(PogsAmdSolver **out, enum ORD ord, size_t m, size_t n, const double *A, int mem,
+                            const PogsAmdOptions *opt);
+
 /* Cold-start solve (reference: PogsImplementation::Solve, src/cpu/pogs.cpp:91-581).
  * Coefficient and output pointers are HOST pointers of the solver's dtype
  * (f_*: m_local, g_*: n; x: n, y/l: m_local).  mu (length n) may be NULL. */
@@ -814,6 +839,27 @@ int PogsAmdDensePassCheck(const PogsAmdDensePassArgs *args);
  * must be NULL.  All vectors are doubles with the length contract above (col_len >= round_up(n, 2)); info as above
  * (kernel = 3).  Invalid arguments are refused before any device work. */
 int PogsAmdDensePassMixedCheck(const PogsAmdDensePassArgs *args);
+/* Diagnostic of the single-vector streaming pass over a FLOAT matrix (csrc/stream_mixed.h: stream_rows_mixed_kernel,
+ * what the recurring launches of a PogsAmdCreateDenseMixed handle's projector run): ONE launch and its second stage
+ * on caller-supplied HOST arrays, through the launch functions and with the functors the solver uses.
+ *   form ACC      (GemvTOp)     tot = M^T u                       (reduce_cols of the column partials); q, scalars untouched
+ *   form DOT_ACC  (DcgQRowOp)   q = M x, tot = M^T q, scalars[0] = |q|^2 (the [grid] records added in order); guarded
+ *   form DOT      (ProjTailOp)  q = M x, scalars[0] = scalars[1] = |q|^2 (its two sums against zero vectors); tot untouched
+ * M is float, rows x ldm, ldm a multiple of 4 and >= round_up(n, 4), its columns n .. round_up(n, 4) zero; columns past
+ * round_up(n, 4) are never read.  x and tot have round_up(n, 2) doubles, u and q `rows`, scalars 2.  num_cu (0: the
+ * device's), force_tpb / force_nv (0 / 0: the plan of n) as PogsAmdDensePassMixedCheck reads them.  `done` is placed in
+ * the guard's slot of a device scalar block before the launch: non-zero, the DOT_ACC launch returns before any load or
+ * store and its second stage is not run, as every launch of an ended CG loop returns at the same flag.
+ * q, tot and scalars are uploaded before the launch and downloaded after it, so what a launch does not write comes
+ * back as given.  The partial buffers start as NaN; `partials` (may be NULL; ACC forms; partials_len
+ * doubles, at least grid * round_up(n, 2) -- checked before the launch) receives the column partials as the launch
+ * left them.  info (8 ints) = {tpb, nv, rows per step, grid, execution tpb,
+ * execution nv, scalar sums per record, workgroups per CU}.  An argument a form does not name may be NULL.  Invalid
+ * arguments are refused before any device work. */
+enum POGS_AMD_STREAM_MIXED_FORM { POGS_AMD_STREAM_MIXED_ACC = 0, POGS_AMD_STREAM_MIXED_DOT_ACC = 1, POGS_AMD_STREAM_MIXED_DOT = 2 };
+int PogsAmdStreamMixedCheck(int form, int rows, int n, const float *M, size_t ldm, int num_cu, int force_tpb, int force_nv,
+                            const double *x, const double *u, double done, double *q, double *tot, double *scalars,
+                            double *partials, size_t partials_len, int *info);
 /* Diagnostic of the kernels that do not read the matrix (csrc/vec_kernels.hip) and of the scalar block's way to the host
  * (csrc/engine.h: Ctx::queue_sum / fetch_scalars): ONE launch (plus the sum launch that follows it in a solve) on
  * caller-supplied HOST arrays, through the launch functions and block-count helpers the solvers call.  Every x-side array

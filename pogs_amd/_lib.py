@@ -116,6 +116,9 @@ lib.PogsAmdCreateSparse.argtypes = [ctypes.POINTER(c_void_p), c_int, c_int, c_si
 lib.PogsAmdCreateSparseMixed.argtypes = [ctypes.POINTER(c_void_p), c_int, c_size_t, c_size_t, c_size_t, c_void_p, c_void_p,
                                          c_void_p, c_int, ctypes.POINTER(PogsAmdOptions)]
 lib.PogsAmdCreateSparseMixed.restype = c_int
+lib.PogsAmdCreateDenseMixed.argtypes = [ctypes.POINTER(c_void_p), c_int, c_size_t, c_size_t, c_void_p, c_int,
+                                        ctypes.POINTER(PogsAmdOptions)]
+lib.PogsAmdCreateDenseMixed.restype = c_int
 lib.PogsAmdSolve.argtypes = [c_void_p] + [c_void_p] * 12 + [c_double, c_double, c_double, c_uint, c_uint, c_int, c_int,
                                                             c_void_p, c_void_p, c_void_p, c_void_p,
                                                             ctypes.POINTER(c_double), ctypes.POINTER(c_uint)]
@@ -278,6 +281,7 @@ ABI_SYMBOLS = [
     "PogsAmdSpmvCheck", "PogsAmdSparseCgCheck", "PogsAmdGetFactor", "PogsAmdSparseGramCheck", "PogsAmdTriMatvecCheck",
     "PogsAmdDensePassCheck", "PogsAmdDenseCgCheck", "PogsAmdVecCheck", "PogsAmdDensePassMixedCheck",
     "PogsAmdCreateSparseMixed", "PogsAmdSpmvMixedCheck", "PogsAmdBatchRowsMixedCheck", "PogsAmdBatchColsMixedCheck",
+    "PogsAmdCreateDenseMixed", "PogsAmdStreamMixedCheck",
 ]
 
 
@@ -685,6 +689,47 @@ def dense_pass_mixed_check(form, M, n, vec, **kw):
     of 4; every vector float64, column-side ones at least round_up(n, 2) long.  Arguments and result as
     dense_pass_check; force names a one-pass shape of the mixed plan."""
     return dense_pass_check(form, M, n, vec, _mixed=True, **kw)
+
+
+lib.PogsAmdStreamMixedCheck.argtypes = [c_int, c_int, c_int, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p,
+                                        c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+lib.PogsAmdStreamMixedCheck.restype = c_int
+STREAM_MIXED_ACC, STREAM_MIXED_DOT_ACC, STREAM_MIXED_DOT = 0, 1, 2
+STREAM_MIXED_INFO = ("tpb", "nv", "rows_per_step", "grid", "exec_tpb", "exec_nv", "ns", "blocks_per_cu")
+
+
+def stream_mixed_check(form, M, n, x=None, u=None, done=0.0, q=None, tot=None, scalars=None, num_cu=0, force=None,
+                       partials=None):
+    """One launch of the single-vector streaming pass over a float32 matrix and its second stage (include/pogs_amd.h:
+    PogsAmdStreamMixedCheck).  M: float32, rows x ldm; x: float64, round_up(n, 2) (DOT forms); u: float64, rows (ACC).
+    q (rows), tot (round_up(n, 2)), scalars (2): what the outputs hold before the launch, NaN by default; partials: an
+    integer N asks for the first N doubles of the column partials.  force: (tpb, nv) or None.  Returns a dict of copies:
+    "q", "tot", "scalars", "partials" (or None) and "info" (dict of STREAM_MIXED_INFO).  The arguments are not changed."""
+    import numpy as np
+    M = np.ascontiguousarray(M)
+    if M.ndim != 2 or M.dtype != np.float32:
+        raise ValueError("M: float32 (rows, ldm)")
+    rows, n_pad = M.shape[0], -(-int(n) // 2) * 2
+
+    def vec(v, length, fill):
+        if v is None:
+            return np.full(length, fill) if fill is not None else None
+        v = np.array(v, dtype=np.float64, order="C", copy=True)
+        if v.shape != (length,):
+            raise ValueError("vector of %d float64 expected, got shape %s" % (length, v.shape))
+        return v
+
+    x, u = vec(x, n_pad, None), vec(u, rows, None)
+    q, tot, scalars = vec(q, rows, np.nan), vec(tot, n_pad, np.nan), vec(scalars, 2, np.nan)
+    part = np.full(int(partials), 0.0) if partials else None
+    info = np.zeros(8, dtype=np.int32)
+    ptr = lambda v: None if v is None else v.ctypes.data   # noqa: E731
+    tpb, nv = (0, 0) if force is None else (int(force[0]), int(force[1]))
+    if lib.PogsAmdStreamMixedCheck(int(form), rows, int(n), M.ctypes.data, M.shape[1], int(num_cu), tpb, nv, ptr(x), ptr(u),
+                                   float(done), ptr(q), ptr(tot), ptr(scalars), ptr(part), 0 if part is None else part.size,
+                                   info.ctypes.data) != 0:
+        raise RuntimeError(last_error())
+    return dict(q=q, tot=tot, scalars=scalars, partials=part, info=dict(zip(STREAM_MIXED_INFO, (int(v) for v in info))))
 
 
 def dense_pass_check(form, M, n, vec, functor=PASS_FN_CHEAP, cols=PASS_COLS_REDUCE, f=None, g=None, rho=1.0, alpha=1.0,

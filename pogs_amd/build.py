@@ -24,7 +24,7 @@ ALIAS = os.path.join(_HERE, "libpogs_cpu.so")
 PLUGIN_SRC = os.path.join(_HERE, "..", "tests", "transport", "test_transport.hip")
 PLUGIN_LIB = os.path.join(_HERE, "..", "tests", "transport", "libpogs_test_transport.so")
 SOURCES = ["abi.hip", "sparse.hip", "gemm.hip", "vec_kernels.hip", "dist.hip", "batch_kernels.hip", "many_kernels.hip",
-           "sparse_batch_kernels.hip", "dense_mixed.hip"]
+           "sparse_batch_kernels.hip", "dense_mixed.hip", "stream_mixed.hip"]
 # dense_plan.hip is compiled once per arithmetic type and streaming shape (csrc/stream.h:
 # POGS_STREAM_PLANS) plus the windowed form -- one small code object per shape, see dense_plan.hip
 PLAN_SOURCE = "dense_plan.hip"

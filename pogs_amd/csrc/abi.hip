@@ -15,6 +15,7 @@
 #include "spmv_check.h"
 #include "prox.h"
 #include "stream.h"
+#include "stream_mixed_check.h"
 #include "vec_check.h"
 #include "vec_kernels.h"
 
@@ -115,6 +116,20 @@ inline void dense_pass_mixed_check(const PogsAmdDensePassArgs *a) {
     num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
   }
   pass_mixed_check_run(*a, num_cu);
+}
+
+// PogsAmdStreamMixedCheck: refusals first (no device), then the launches (stream_mixed_check.h)
+inline void stream_mixed_check(const StreamMixedCheckArgs &a) {
+  stream_mixed_check_validate(a);
+  int num_cu = a.num_cu;
+  if (num_cu == 0) {
+    int dev = 0;
+    hipDeviceProp_t prop;
+    POGS_HIP_CHECK(hipGetDevice(&dev));
+    POGS_HIP_CHECK(hipGetDeviceProperties(&prop, dev));
+    num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+  }
+  stream_mixed_check_run(a, num_cu);
 }
 
 SolverBase *make_sparse_solver(int dtype, int ord, size_t m, size_t n, size_t nnz, const void *data,
@@ -424,6 +439,31 @@ int PogsAmdCreateSparseMixed(PogsAmdSolver **out, enum ORD ord, size_t m, size_t
     DeviceGuard guard(opt ? opt->device : -1);
     new_handle(out,
                [&] { return make_sparse_solver_mixed(static_cast<int>(ord), m, n, nnz, data, ptr, ind, mem, opt); });
+    return 0;
+  });
+}
+
+int PogsAmdCreateDenseMixed(PogsAmdSolver **out, enum ORD ord, size_t m, size_t n, const double *A, int mem,
+                            const PogsAmdOptions *opt) {
+  return guarded([&]() {
+    POGS_CHECK(out != nullptr, "null argument: out");
+    *out = nullptr;
+    // every refusal comes before anything is built (and before the first HIP call)
+    POGS_CHECK(A && opt, "null argument: A and opt are required (opt->projector names POGS_AMD_PROJ_CGLS_FUSED)");
+    POGS_CHECK(ord == ROW_MAJ || ord == COL_MAJ, "unknown ord (ROW_MAJ or COL_MAJ)");
+    POGS_CHECK(mem == POGS_AMD_HOST || mem == POGS_AMD_DEVICE, "unknown mem (POGS_AMD_HOST or POGS_AMD_DEVICE)");
+    POGS_CHECK(m > 0 && n > 0 && m < (1u << 31) && n < (1u << 31), "bad dimensions");
+    POGS_CHECK(opt->projector == POGS_AMD_PROJ_CGLS_FUSED,
+               "a mixed dense handle runs the one-pass CGLS projector: opt->projector must be POGS_AMD_PROJ_CGLS_FUSED "
+               "(the direct projector over a float copy: PogsAmdCreateDense with POGS_AMD_STORE_F32)");
+    POGS_CHECK(PogsAmdOptStorage(opt) == POGS_AMD_STORE_SAME || PogsAmdOptStorage(opt) == POGS_AMD_STORE_F32,
+               "storage: unknown value (a mixed dense handle takes 0 or POGS_AMD_STORE_F32; it keeps the float copy either way)");
+    POGS_CHECK(make_mixed_plan(n, 256).ok,
+               "the row is too wide for a mixed dense handle (windowed, or past the 10240 columns of the mixed plan's one-pass shapes)");
+    PogsAmdOptions o = *opt;
+    PogsAmdOptStorage(&o) = POGS_AMD_STORE_F32;
+    DeviceGuard guard(o.device);
+    new_handle(out, [&] { return make_dense_solver(POGS_AMD_F64, static_cast<int>(ord), m, n, A, mem, &o, nullptr); });
     return 0;
   });
 }
@@ -975,6 +1015,16 @@ int PogsAmdSparseCgCheck(PogsAmdSolver *s, const void *x0, const void *y0, const
     DeviceGuard guard(s->impl->device());
     s->impl->sparse_cg_check(SparseCgCheckArgs{x0, y0, x_warm, y_warm, x_prev, x12, y12, tol, max_steps, ahead, ysync, loop,
                                                x, y_new, xtemp, ytemp, r, p, sv, slots, rec_x, info, enqueued});
+    return 0;
+  });
+}
+
+int PogsAmdStreamMixedCheck(int form, int rows, int n, const float *M, size_t ldm, int num_cu, int force_tpb, int force_nv,
+                            const double *x, const double *u, double done, double *q, double *tot, double *scalars,
+                            double *partials, size_t partials_len, int *info) {
+  return guarded([&]() {
+    stream_mixed_check(StreamMixedCheckArgs{form, rows, n, M, ldm, num_cu, force_tpb, force_nv, x, u, done, q, tot, scalars,
+                                            partials, partials_len, info});
     return 0;
   });
 }

@@ -29,22 +29,7 @@
 // Member definitions of the class template declared in dense_solver.h, which includes this file once, right after the
 // class, inside its namespaces (no include guard, no namespace of its own); the kernels and functors of the loop first.
 
-// L1's row functor: q_i = dot, |q|^2, and q_i back as the coefficient of row i in the column sums t = A^T q.
-template <typename T>
-struct DcgQRowOp {
-  static constexpr int NS = 1;
-  static constexpr bool kGuarded = true;
-  T *q;
-  const double *S;
-  __device__ __forceinline__ bool skip() const { return S[kFcDone] != 0.0; }
-  template <int N>
-  __device__ __forceinline__ T row(int i, T dot, double (&s)[N]) const {
-    q[i] = dot;
-    dev::prod_acc(s[0], dot, dot);
-    return dot;
-  }
-  __device__ __forceinline__ T u(int) const { return 0; }
-};
+// (L1's row functor, DcgQRowOp, is in stream_mixed.h: the mixed launch functions name it)
 
 // start: s_j = (A^T r)_j - shift x_j ; p_j = s_j ; |s_0|^2                  (cgls.h:236-245)
 template <typename T>
@@ -209,7 +194,8 @@ void DenseSolver<T, Tag>::alloc_cg_fused() {
   const size_t pb = static_cast<size_t>(pre_blocks(n_)) + pre_blocks(m_);
   size_t off = 0;
   auto take = [&](size_t cnt) { const size_t o = off; off += cnt + 8; return o; };
-  cgo_q_ = take(static_cast<size_t>(planA_.grid_max));
+  // (the |q|^2 records are the launch's own grid: the larger of planA_'s and, on a mixed-storage handle, the mixed plan's)
+  cgo_q_ = take(std::max<size_t>(planA_.grid_max, mixed_store_ ? mixed1_grid_max(planM_) : 0));
   cgo_p_ = take(kCgfBlocks);
   cgo_x_ = take(nbx);
   cgo_s_ = take(nbx);
@@ -237,11 +223,13 @@ const double *DenseSolver<T, Tag>::cg_loop_fused(T *x, const T *xprev, const T *
   double *rec_s = cgf_rec_.p + cgo_s_, *rec_s0 = cgf_rec_.p + cgo_s0_, *cpart = cgf_rec_.p + cgo_close_;
   const double shift = 1.0, kEps = std::numeric_limits<T>::epsilon();
   const int gp = cgf_blocks(n_), gy = cgf_blocks(m_), gxa = dcg_blocks_x(n_pad_, VEC);
-  const int gridQ = stream_grid<true, true>(planA_, m_);
-  const unsigned long long reads_per_step = planA_.xl ? 2 : 1;   // windowed: dot windows, then column windows
+  // mixed storage: the start's column-sum pass and L1 read the float copy (stream_mixed.h) -- their own grids
+  const bool mixed = mixed_cg();
+  const int gridQ = cg_grid(true, true);
+  const unsigned long long reads_per_step = (planA_.xl && !mixed) ? 2 : 1;   // windowed: dot windows, then column windows
   // u = A^T r ; s = u - shift x ; p = s ; |s_0|^2 records                     (cgls.h:236-245)
-  gemv_t_partials(cg_r_.p);
-  launch_reduce_cols<T, DcgInitColOp<T>>(colpart_.p, stream_grid<false, true>(planA_, m_), n_pad_,
+  cg_gemv_t_partials(cg_r_.p);
+  launch_reduce_cols<T, DcgInitColOp<T>>(colpart_.p, cg_grid(false, true), n_pad_,
                                          DcgInitColOp<T>{x, static_cast<T>(shift), cg_s_.p, cg_p_.p, n_}, rec_s0, s);
   ctx_.stats.matvecs += 1;
   const int nrec_s0 = reduce_cols_grid(n_pad_, VEC);
@@ -253,8 +241,15 @@ const double *DenseSolver<T, Tag>::cg_loop_fused(T *x, const T *xprev, const T *
     StreamArgs<T> sa = argsA();
     sa.xin = cg_p_.p;
     sa.scalar_partials = rec_q;
-    ev.push_back(ctx_.stream_timer.begin(s));
-    launch_stream<T, true, true, false, kFull, Tag>(planA_, sa, DcgQRowOp<T>{cg_q_.p, S}, s);
+    ev.push_back(cg_tbegin(kCgFormL1));
+    bool done = false;
+    if constexpr (std::is_same<T, double>::value) {
+      if (mixed) {
+        launch_stream_mixed(planM_, argsM(cg_p_.p, rec_q), DcgQRowOp<double>{cg_q_.p, S}, s);
+        done = true;
+      }
+    }
+    if (!done) launch_stream<T, true, true, false, kFull, Tag>(planA_, sa, DcgQRowOp<T>{cg_q_.p, S}, s);
     ctx_.stream_timer.end(s);
     // L2
     DcgStepA<T> a;
@@ -311,6 +306,8 @@ const double *DenseSolver<T, Tag>::cg_loop_fused(T *x, const T *xprev, const T *
   // launches that found the loop ended were no-ops: they read nothing
   ctx_.stats.matvecs += reads_per_step * static_cast<unsigned long long>(steps);
   for (size_t k = static_cast<size_t>(steps); k < ev.size(); ++k) ctx_.stream_timer.drop(ev[k]);
+  if (mixed)   // (the bracketed launches that ran read the float copy: collect_timer)
+    for (size_t k = 0; k < ev.size() && k < static_cast<size_t>(steps); ++k) mixed_timed_ += ev[k] != EventTimer::npos;
   if (enqueued) *enqueued = enq;
   return Sh;
 }
@@ -328,10 +325,18 @@ const double *DenseSolver<T, Tag>::project_cg_fused(int nw, bool ysync, int ahea
     // y = A x fused with the y half's bookkeeping                             (projector_cgls.cpp:78)
     StreamArgs<T> a = argsA();
     a.xin = x_[nw].p;
-    ctx_.stream_timer.begin(s);
-    launch_stream<T, true, false, false, kFull, Tag>(planA_, a, ProjTailOp<T>{y_[nw].p, y_[cur_].p, y12_.p, ytemp_.p}, s);
+    const bool timed = cg_tbegin(kCgFormYsync) != EventTimer::npos;
+    bool done = false;
+    if constexpr (std::is_same<T, double>::value) {
+      if (mixed_cg()) {
+        launch_stream_mixed(planM_, argsM(x_[nw].p, ctx_.spart.p), ProjTailOp<double>{y_[nw].p, y_[cur_].p, y12_.p, ytemp_.p}, s);
+        mixed_timed_ += timed;
+        done = true;
+      }
+    }
+    if (!done) launch_stream<T, true, false, false, kFull, Tag>(planA_, a, ProjTailOp<T>{y_[nw].p, y_[cur_].p, y12_.p, ytemp_.p}, s);
     ctx_.stream_timer.end(s);
-    sum_row_scalars(stream_grid<true, false>(planA_, m_), 2, ctx_.S.p + kDYprev2);
+    sum_row_scalars(cg_grid(true, false), 2, ctx_.S.p + kDYprev2);
     ctx_.stats.matvecs += 1;
     Sh = ctx_.fetch_scalars();
   }

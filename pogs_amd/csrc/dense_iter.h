@@ -152,7 +152,7 @@ bool DenseSolver<T, Tag>::iteration(unsigned verbose) {
       launch_sum_jobs(&j, 1, s);
     } else {
       a.xin = x12_.p;
-      ctx_.stream_timer.begin(s);
+      cg_tbegin(kCgFormOther);   // (bracketed as ever, unless POGS_AMD_CG_TIME_FORM names one form of the fused loop)
       launch_stream<T, true, true, false, kFull, Tag>(planA_, a,
                                                  ExactRowOp<T>{y12_.p, yt_.p, y_[cur_].p, zt_scale_}, s);
       ctx_.stream_timer.end(s);

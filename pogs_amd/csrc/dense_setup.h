@@ -78,7 +78,11 @@ void DenseSolver<T, Tag>::alloc_state() {
   if (tmode_) { uvec_.alloc(mp); uvec_.zero(s); }
   // (mixed storage: the mixed plan's launches may use more workgroups than planA_'s -- the partial-sum buffers take
   //  the larger of the two)
-  const size_t gmax = std::max<size_t>(planA_.grid_max, mixed_store_ ? mixed_grid_max(planM_) : 0);
+  const size_t gmax = std::max<size_t>(planA_.grid_max, !mixed_store_ ? 0 : cg_fused_ ? mixed1_grid_max(planM_) : mixed_grid_max(planM_));
+  // (the y-sync product of a mixed fused-CGLS handle leaves [grid][2] sums in the first region of the scalar scratch,
+  //  which other launches address as planA_.grid_max * 6)
+  POGS_CHECK(!(mixed_store_ && cg_fused_) || static_cast<size_t>(mixed1_grid_max(planM_)) * 2 <= static_cast<size_t>(planA_.grid_max) * 6,
+             "POGS_AMD_STORE_F32: the mixed plan's grid does not fit the scalar scratch");
   colpart_.alloc(gmax * scols_pad_);
   ensure_xl(planA_, srows_, scols_pad_);
   if (use_cgls_) {
@@ -111,9 +115,10 @@ void DenseSolver<T, Tag>::alloc_state() {
   ctx_.ensure_spart(sp_tail_off_ + static_cast<size_t>(ctx_.num_cu) * 32);
   if (mixed_store_) {
     A32_.alloc(static_cast<size_t>(m_) * lda32_);
-    // POGS_AMD_MIXED_PASS=0: the matrix is still rounded and both copies built, but step (D) stays on A_ (A / B leg)
+    // POGS_AMD_MIXED_PASS=0: the matrix is still rounded and both copies built, but step (D) -- on a fused-CGLS handle
+    // the loop's recurring launches -- stays on A_ (A / B leg)
     const char *mp = std::getenv("POGS_AMD_MIXED_PASS");
-    mixed_pass_ = fused_ok_ && !(mp && mp[0] == '0');
+    mixed_pass_ = (cg_fused_ || fused_ok_) && !(mp && mp[0] == '0');
     const char *mf = std::getenv("POGS_AMD_MIXED_FULL");
     mixed_full_ = mixed_pass_ && mf && mf[0] == '1';
   }

@@ -152,10 +152,17 @@ class DenseSolver final : public SoloSolver<T> {
     cg_fused_ = opt && opt->projector == POGS_AMD_PROJ_CGLS_FUSED;
     use_cgls_ = cg_fused_ || (opt && opt->projector == POGS_AMD_PROJ_CGLS);
     if (const char *ys = std::getenv("POGS_AMD_YSYNC")) ysync_ = std::max(0, std::atoi(ys));
+    // measurement aid (scripts/dense_cgls_mixed_throughput.py): with profiling on, bracket only ONE of the fused loop's
+    // recurring launches -- 1 the start's A^T r, 2 L1, 3 the y-sync product -- so that stream_ms / stream_launches is
+    // that form's mean time
+    if (const char *tf = std::getenv("POGS_AMD_CG_TIME_FORM")) cg_time_form_ = std::atoi(tf);
     // mixed storage (stream_mixed.h; the combinations it is honoured for are checked in abi.hip before anything is built)
     mixed_store_ = std::is_same<T, double>::value && opt && PogsAmdOptStorage(opt) == POGS_AMD_STORE_F32;
     if (mixed_store_) {
-      POGS_CHECK(tall_ && !multi_ && !use_cgls_, "POGS_AMD_STORE_F32 needs m > n, the direct projector and one GPU");
+      // two kinds of handle: the direct projector for m > n (the one-pass iteration reads the float copy), and the
+      // one-pass CGLS projector for any shape (the loop's recurring launches do: dense_cg_fused.h)
+      POGS_CHECK(!multi_ && (cg_fused_ || (tall_ && !use_cgls_)),
+                 "POGS_AMD_STORE_F32 needs one GPU and either m > n with the direct projector or POGS_AMD_PROJ_CGLS_FUSED");
       planM_ = make_mixed_plan(n, ctx_.num_cu);
       POGS_CHECK(planM_.ok, "POGS_AMD_STORE_F32: the row fits no one-pass shape of the mixed plan");
       lda32_ = round_up(n, 4);
@@ -467,6 +474,34 @@ class DenseSolver final : public SoloSolver<T> {
 
   // ---- the one-pass, device-resident CGLS loop (POGS_AMD_PROJ_CGLS_FUSED; dense_cg_fused.h) ----
   void alloc_cg_fused();
+  // Mixed storage on such a handle: the loop's three recurring launches -- the start's A^T r, L1 of every step, the
+  // y-sync product -- read A32_ through stream_rows_mixed_kernel (stream_mixed.h), with the mixed plan's grids; every
+  // other pass stays on A_ (equal numbers).
+  bool mixed_cg() const { return cg_fused_ && mixed_pass_; }
+  int cg_grid(bool dot, bool acc) const {
+    if (mixed_cg()) return mixed1_grid(planM_, dot, acc, m_);
+    return dot && acc ? stream_grid<true, true>(planA_, m_) : dot ? stream_grid<true, false>(planA_, m_) : stream_grid<false, true>(planA_, m_);
+  }
+  StreamArgsMixed1 argsM(const double *xin, double *scalar_partials) const {
+    return StreamArgsMixed1{A32_.p, lda32_, m_, n_pad_, static_cast<int>(lda32_), xin, colpart_.p, scalar_partials};
+  }
+  enum { kCgFormStart = 1, kCgFormL1 = 2, kCgFormYsync = 3, kCgFormOther = 4 };
+  size_t cg_tbegin(int form) {   // (POGS_AMD_CG_TIME_FORM; EventTimer::end without a begin does nothing)
+    return (cg_time_form_ == 0 || cg_time_form_ == form) ? ctx_.stream_timer.begin(ctx_.stream) : EventTimer::npos;
+  }
+  void cg_gemv_t_partials(const T *u) {   // the start of a projection: col partials <- A^T u
+    const bool timed = cg_tbegin(kCgFormStart) != EventTimer::npos;
+    bool done = false;
+    if constexpr (std::is_same<T, double>::value) {
+      if (mixed_cg()) {
+        launch_stream_mixed(planM_, argsM(nullptr, nullptr), GemvTOp<double>{1, u}, ctx_.stream);
+        mixed_timed_ += timed;
+        done = true;
+      }
+    }
+    if (!done) launch_stream<T, false, true, false, kFull, Tag>(planA_, argsA(), GemvTOp<T>{1, u}, ctx_.stream);
+    ctx_.stream_timer.end(ctx_.stream);
+  }
   const double *cg_loop_fused(T *x, const T *xprev, const T *ycur, T *ynew, int ahead_steps, int max_steps, double tol,
                               const double *pre_part, int *enqueued);
   const double *project_cg_fused(int nw, bool ysync, int ahead, int max_steps, double tol, const double *pre_part,
@@ -524,13 +559,15 @@ class DenseSolver final : public SoloSolver<T> {
   DevBuf<double> cg_;
   bool cg_fused_ = false;       // POGS_AMD_PROJ_CGLS_FUSED (use_cgls_ is set too)
   int cg_pred_ = 1;             // fused loop: CG steps enqueued ahead, what the previous projection took
+  int cg_time_form_ = 0;        // POGS_AMD_CG_TIME_FORM (measurement aid): the one form of the loop's launches that is timed
   DevBuf<double> cgf_rec_;      // fused loop: the per-block records and the partial sums of its launches
   size_t cgo_q_ = 0, cgo_p_ = 0, cgo_x_ = 0, cgo_s_ = 0, cgo_s0_ = 0, cgo_pre_ = 0, cgo_close_ = 0;   // regions of cgf_rec_
   std::vector<size_t> cgf_events_;   // fused loop: the timer brackets of the enqueued passes
   size_t lda_ = 0;
   StreamPlan planA_, planW_;
   // mixed storage (POGS_AMD_STORE_F32, stream_mixed.h): A_ holds the rounded matrix, A32_ the same values as floats
-  // (m x lda32_, lda32_ = round_up(n, 4), zero padding); step (D) of iteration_fused reads A32_ when mixed_pass_
+  // (m x lda32_, lda32_ = round_up(n, 4), zero padding); step (D) of iteration_fused reads A32_ when mixed_pass_, and on
+  // a fused-CGLS handle the loop's recurring launches do (mixed_cg())
   bool mixed_store_ = false, mixed_pass_ = false;
   bool mixed_full_ = false;     // POGS_AMD_MIXED_FULL=1 (measurement aid): the full form from the first iteration
   MixedPlan planM_;

@@ -27,12 +27,17 @@
 //     stream_rows2_kernel.
 //   * GRIDS.  The grid may exceed the number of row blocks: an idle workgroup still writes zero column partials and
 //     zero scalar partials, as the second stage adds [grid] records.
+//
+// The second half of this file is the same idea for the one-pass CGLS projector (POGS_AMD_PROJ_CGLS_FUSED with
+// POGS_AMD_STORE_F32, any shape: PogsAmdCreateDenseMixed): stream_rows_mixed_kernel, the single-vector pass in the
+// three forms the device-resident loop launches, in its own translation unit (stream_mixed.hip).
 #include <hip/hip_runtime.h>
 
 #include "common.h"
 #include "ops.h"
 #include "reduce.h"
 #include "stream.h"
+#include "vec_kernels.h"
 
 namespace pogs_amd {
 
@@ -275,6 +280,224 @@ __global__ void __launch_bounds__(TPB, mixed_waves_per_simd(TPB, NV, NA)) stream
       const int c = (v * TPB + t) * 4;
       if (c < a.n32) *reinterpret_cast<double2 *>(out + c) = acc[q][2 * v];
       if (c + 2 < a.n_pad) *reinterpret_cast<double2 *>(out + c + 2) = acc[q][2 * v + 1];
+    }
+  }
+  if (Op::NS > 0) {
+    __syncthreads();
+    dev::block_sum<NS, TPB>(sacc, s_red);
+    if (t == 0) {
+#pragma unroll
+      for (int k = 0; k < NS; ++k) a.scalar_partials[static_cast<size_t>(bid) * NS + k] = sacc[k];
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// stream_rows_mixed_kernel: the SINGLE-VECTOR streaming pass over the float copy, for the one-pass CGLS projector of a
+// mixed-storage handle (dense_cg_fused.h).  The contract of stream_rows_kernel<double, ...> (stream.h) over a float
+// matrix: the same Op interface (row(i, dot, s) returns the row's coefficient, u(i) for the ACC-only form, NS scalar
+// sums, kGuarded / skip() through StreamOpGuarded), column partials [grid][n_pad] in DOUBLES, scalar partials
+// [grid][NS], one fixed order of every sum, no atomics.  Rows, the column-partial slot and the scalar-partial slot go
+// by the logical workgroup id of the one-pass kernels (stream.h: a bijection, so every sum is what blockIdx.x gives).
+// The tile handling is stream_rows2_mixed_kernel's: float4 non-temporal loads, unconditional on clamped rows and
+// columns; the tile stays in floats and is widened where it is used; a float vector is two pairs of doubles, the upper
+// pair present only where c + 2 < n_pad; a row past m is zeroed by a mask.  Three forms:
+//   ACC       u = A^T r at the start of every projection            GemvTOp<double>    (no x vector, no barrier)
+//   DOT + ACC L1 of every CG step: q = A p, |q|^2, t = A^T q         DcgQRowOp<double>  (guarded)
+//   DOT       y = A x of the y-sync projection                       ProjTailOp<double> (no accumulators, one barrier)
+// A guarded launch that finds the loop ended returns before any load or store.  An idle workgroup (grid larger than
+// the number of row blocks) writes zero column partials and zero scalar partials.
+// ---------------------------------------------------------------------------------------------------------------------
+
+// L1's row functor of the device-resident CGLS loop (dense_cg_fused.h): q_i = dot, |q|^2, and q_i back as the
+// coefficient of row i in the column sums t = A^T q.  It lives here, outside the per-shape objects' unnamed namespace,
+// because the launch functions below name it.
+template <typename T>
+struct DcgQRowOp {
+  static constexpr int NS = 1;
+  static constexpr bool kGuarded = true;
+  T *q;
+  const double *S;
+  __device__ __forceinline__ bool skip() const { return S[kFcDone] != 0.0; }
+  template <int N>
+  __device__ __forceinline__ T row(int i, T dot, double (&s)[N]) const {
+    q[i] = dot;
+    dev::prod_acc(s[0], dot, dot);
+    return dot;
+  }
+  __device__ __forceinline__ T u(int) const { return 0; }
+};
+
+struct StreamArgsMixed1 {
+  const float *A;            // as StreamArgsMixed::A
+  size_t lda;
+  int m;
+  int n_pad, n32;            // round_up(n, 2), round_up(n, 4)
+  const double *xin;         // DOT: n_pad doubles
+  double *col_partials;      // ACC: [grid][n_pad]
+  double *scalar_partials;   // Op::NS > 0: [grid][Op::NS]
+};
+
+// Rows per step and workgroups per CU, as for the one-pass kernel above.  Per thread, in 32-bit registers:
+//   the tile 4 NV R (floats)  +  the x vector 8 NV (DOT)  +  the accumulators 8 NV (ACC)  +  ~40
+// (addresses, the widened entries of the row at hand, one or two scalar sums, a cheap functor: no prox).  DOT-only
+// holds no accumulators and ACC-only no x vector, so they take more rows per step at the same budget.  What the
+// compiler reports for every instance is in DESIGN.md section 3.10; none uses scratch.
+constexpr int mixed1_regs_est(int nv, int r, bool dot, bool acc) { return 4 * nv * r + 8 * nv * ((dot ? 1 : 0) + (acc ? 1 : 0)) + 40; }
+constexpr int mixed1_rows_fit(int nv, bool dot, bool acc, int budget) {
+  return mixed1_regs_est(nv, 8, dot, acc) <= budget ? 8 : mixed1_regs_est(nv, 4, dot, acc) <= budget ? 4
+         : mixed1_regs_est(nv, 3, dot, acc) <= budget ? 3 : mixed1_regs_est(nv, 2, dot, acc) <= budget ? 2
+         : mixed1_regs_est(nv, 1, dot, acc) <= budget ? 1 : 0;
+}
+// (the three functions below take the EXECUTION shape, mixed_exec_tpb / mixed_exec_nv)
+constexpr int mixed1_blocks_per_cu(int tpb, int nv, bool dot, bool acc) {
+  if (tpb == 512) return 1;
+  if (tpb != 256) return 8;
+  const int r3 = 3 * mixed1_rows_fit(nv, dot, acc, 168), r2 = 2 * mixed1_rows_fit(nv, dot, acc, 256);
+  return (r3 >= r2 && r3 > 0) ? 3 : 2;
+}
+constexpr int mixed1_rows_c(int tpb, int nv, bool dot, bool acc) {
+  return mixed1_rows_fit(nv, dot, acc, (tpb == 256 && mixed1_blocks_per_cu(tpb, nv, dot, acc) == 3) ? 168 : 256);
+}
+constexpr int mixed1_waves_per_simd(int tpb, int nv, bool dot, bool acc) {
+  return (mixed1_blocks_per_cu(tpb, nv, dot, acc) * (tpb / 64) + 3) / 4;
+}
+inline int mixed1_rows(const MixedPlan &p, bool dot, bool acc) {
+  return mixed1_rows_c(mixed_exec_tpb(p.tpb, p.nv), mixed_exec_nv(p.tpb, p.nv), dot, acc);
+}
+inline int mixed1_grid_cap(const MixedPlan &p, bool dot, bool acc) {
+  return p.num_cu * mixed1_blocks_per_cu(mixed_exec_tpb(p.tpb, p.nv), mixed_exec_nv(p.tpb, p.nv), dot, acc);
+}
+inline int mixed1_grid_max(const MixedPlan &p) {
+  return std::max(mixed1_grid_cap(p, false, true), std::max(mixed1_grid_cap(p, true, true), mixed1_grid_cap(p, true, false)));
+}
+inline int mixed1_grid(const MixedPlan &p, bool dot, bool acc, int m) {
+  const int R = mixed1_rows(p, dot, acc), nblk = (m + R - 1) / R, gmax = mixed1_grid_cap(p, dot, acc);
+  return nblk < gmax ? (nblk > 0 ? nblk : 1) : gmax;
+}
+
+// The launches (stream_mixed.hip); the functor's type names the form.
+void launch_stream_mixed(const MixedPlan &p, const StreamArgsMixed1 &a, const GemvTOp<double> &op, hipStream_t s);     // ACC
+void launch_stream_mixed(const MixedPlan &p, const StreamArgsMixed1 &a, const DcgQRowOp<double> &op, hipStream_t s);   // DOT + ACC
+void launch_stream_mixed(const MixedPlan &p, const StreamArgsMixed1 &a, const ProjTailOp<double> &op, hipStream_t s);  // DOT
+
+template <int TPB, int NV, int R, bool DOT, bool ACC, typename Op>
+__global__ void __launch_bounds__(TPB, mixed1_waves_per_simd(TPB, NV, DOT, ACC)) stream_rows_mixed_kernel(StreamArgsMixed1 a, Op op) {
+  static_assert(DOT || ACC, "a pass forms row dots, column sums or both");
+  static_assert(R >= 1 && R <= 64, "the row functor runs on the lanes t < R of the first wavefront");
+  if constexpr (StreamOpGuarded<Op>::value) {
+    if (op.skip()) return;
+  }
+  constexpr int NW = TPB / 64;
+  constexpr int NS = Op::NS > 0 ? Op::NS : 1;
+  constexpr int NX = DOT ? NV : 1, NACC = ACC ? 2 * NV : 1;
+  __shared__ double s_part[2 * R * NW];
+  __shared__ double s_u[2 * R];
+  __shared__ double s_red[NS * NW];
+  const unsigned bid = dev::logical_block_id();
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+
+  // float vector v of this thread covers columns c .. c + 3, c = (v TPB + t) 4: the pair (c, c + 1) exists in the
+  // x-side vectors whenever c < n32, the pair (c + 2, c + 3) only if c + 2 < n_pad (stream_rows2_mixed_kernel)
+  double2 xlo[NX], xhi[NX];
+  double2 acc[NACC];
+  int colc[NV];   // the column a lane loads: its own, or (past n32) the row's last vector
+#pragma unroll
+  for (int v = 0; v < NV; ++v) {
+    const int c = (v * TPB + t) * 4;
+    const bool lo = c < a.n32, hi = c + 2 < a.n_pad;
+    colc[v] = lo ? c : a.n32 - 4;
+    if (DOT) {
+      xlo[v] = lo ? *reinterpret_cast<const double2 *>(a.xin + c) : make_double2(0.0, 0.0);
+      xhi[v] = hi ? *reinterpret_cast<const double2 *>(a.xin + c + 2) : make_double2(0.0, 0.0);
+    }
+  }
+  if (ACC) {
+#pragma unroll
+    for (int v = 0; v < 2 * NV; ++v) acc[v] = make_double2(0.0, 0.0);
+  }
+  double sacc[NS];
+#pragma unroll
+  for (int k = 0; k < NS; ++k) sacc[k] = 0.0;
+
+  const int nblk = (a.m + R - 1) / R;
+  int slot = 0;
+  for (int blk = bid; blk < nblk; blk += gridDim.x, slot ^= 1) {
+    const int row0 = blk * R;
+    // every tile load unconditional: row and column clamped into the matrix, a row past m zeroed by a mask; a lane past
+    // n32 reads the row's last vector again -- its x entries are zero and its partials are never stored
+    float4 av[R][NV];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const int row = row0 + r;
+      const float *rp = a.A + static_cast<size_t>(row < a.m ? row : a.m - 1) * a.lda;
+      const unsigned keep = row < a.m ? 0xFFFFFFFFu : 0u;
+#pragma unroll
+      for (int v = 0; v < NV; ++v) {
+        typedef unsigned int raw16 __attribute__((ext_vector_type(4)));
+        const float4 val = stream_load<float4>(rp + colc[v]);
+        raw16 bits;
+        __builtin_memcpy(&bits, &val, 16);
+        bits &= keep;
+        __builtin_memcpy(&av[r][v], &bits, 16);
+      }
+    }
+    if (DOT) {
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        double s0 = 0;
+#pragma unroll
+        for (int v = 0; v < NV; ++v) {
+          const double2 alo = make_double2(static_cast<double>(av[r][v].x), static_cast<double>(av[r][v].y));
+          const double2 ahi = make_double2(static_cast<double>(av[r][v].z), static_cast<double>(av[r][v].w));
+          s0 += dev::vdot(alo, xlo[v]);
+          s0 += dev::vdot(ahi, xhi[v]);
+        }
+        s0 = dev::wave_sum(s0);
+        if (lane == 0) s_part[(slot * R + r) * NW + wave] = s0;
+      }
+      __syncthreads();
+      if (t < R) {
+        const int row = row0 + t;
+        double uval = 0;
+        if (row < a.m) {
+          double dot = 0;
+#pragma unroll
+          for (int w = 0; w < NW; ++w) dot += s_part[(slot * R + t) * NW + w];
+          uval = op.row(row, dot, sacc);
+        }
+        if (ACC) s_u[slot * R + t] = uval;
+      }
+      if (ACC) __syncthreads();
+    }
+    if (ACC) {
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        double u;
+        if (DOT) {
+          u = s_u[slot * R + r];
+        } else {
+          u = (row0 + r < a.m) ? op.u(row0 + r) : 0.0;
+        }
+#pragma unroll
+        for (int v = 0; v < NV; ++v) {
+          // (opaque floats: the doubles of the dot phase are not kept alive across the functor, stream_rows2_mixed_kernel)
+          if (DOT) asm volatile("" : "+v"(av[r][v].x), "+v"(av[r][v].y), "+v"(av[r][v].z), "+v"(av[r][v].w));
+          const double2 alo = make_double2(static_cast<double>(av[r][v].x), static_cast<double>(av[r][v].y));
+          const double2 ahi = make_double2(static_cast<double>(av[r][v].z), static_cast<double>(av[r][v].w));
+          dev::vfma(acc[2 * v], u, alo);
+          dev::vfma(acc[2 * v + 1], u, ahi);
+        }
+      }
+    }
+  }
+  if (ACC) {
+    double *out = a.col_partials + static_cast<size_t>(bid) * a.n_pad;
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+      const int c = (v * TPB + t) * 4;
+      if (c < a.n32) *reinterpret_cast<double2 *>(out + c) = acc[2 * v];
+      if (c + 2 < a.n_pad) *reinterpret_cast<double2 *>(out + c + 2) = acc[2 * v + 1];
     }
   }
   if (Op::NS > 0) {

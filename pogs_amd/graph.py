@@ -758,8 +758,11 @@ class Solver:
     ``storage``: None / np.float64 on a float64 solver / STORE_SAME: the matrix is stored in ``dtype``.  np.float32 or
     STORE_F32 with ``dtype=np.float64`` (dense, m > n, direct projector, one GPU, n <= 10240): mixed storage -- the
     equilibrated matrix is rounded to float32 and the handle solves, in float64 arithmetic, the problem of that rounded
-    matrix; ``solve`` and ``iterate`` read the float32 copy (1.5 x the matrix memory; PogsAmdCreateDense).  The
-    attribute ``storage`` holds STORE_SAME or STORE_F32.
+    matrix; ``solve`` and ``iterate`` read the float32 copy (1.5 x the matrix memory; PogsAmdCreateDense).  The same
+    with ``projector=PROJ_CGLS_FUSED`` (dense, ANY shape -- tall or wide --, one GPU, n <= 10240; a host array or a
+    device pointer with ``shape=``): the projector's recurring launches -- A^T r at the start of a projection, the one
+    pass of every CG step, the y-sync product -- read the float32 copy (PogsAmdCreateDenseMixed).  With any other
+    projector ``storage`` keeps needing m > n.  The attribute ``storage`` holds STORE_SAME or STORE_F32.
     ``values``: None / np.float64: as ``dtype``.  np.float32 with ``dtype=np.float64`` on a SPARSE matrix (scipy, or the
     device-CSR tuple; one GPU, projector DEFAULT / CGLS / DIRECT): mixed storage -- the equilibrated non-zeros are
     rounded to float32 and the handle solves, in float64 arithmetic, the problem of that rounded matrix; every solo
@@ -826,8 +829,13 @@ class Solver:
                 A = np.asarray(A, dtype=self.dtype, order="C" if order == Ordering.ROW_MAJ else "F")
                 self.m, self.n = A.shape
                 ptr_val, mem = _ptr(A), _lib.HOST
-            st = lib.PogsAmdCreateDense(ctypes.byref(self._h), code, int(order), self.m, self.n, ptr_val, mem,
-                                        ctypes.byref(opt), dist_p)
+            if self.storage == STORE_F32 and projector == _lib.PROJ_CGLS_FUSED and self.dtype == np.float64 and dist is None:
+                # mixed storage with the one-pass CGLS projector (any shape) has an entry of its own; every other
+                # combination goes to PogsAmdCreateDense, which honours or refuses it as before
+                st = lib.PogsAmdCreateDenseMixed(ctypes.byref(self._h), int(order), self.m, self.n, ptr_val, mem, ctypes.byref(opt))
+            else:
+                st = lib.PogsAmdCreateDense(ctypes.byref(self._h), code, int(order), self.m, self.n, ptr_val, mem,
+                                            ctypes.byref(opt), dist_p)
         if st != 0:
             raise RuntimeError("pogs_amd: solver creation failed: " + _lib.last_error())
         _LIVE_SOLVERS.add(self)
